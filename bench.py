@@ -20,7 +20,12 @@ the beam stages decide for a whole beam at once; `walked_mrays_s` counts only th
 rays walked one by one, and ms_per_step / reference_equivalent_mrays_s are the
 figures to compare with the reference.
 
-Also on the same JSON line:
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline needs: it uploads the scene,
+renders W warmup frames, times K frames, renders one instrumented frame (the rays per frame that `value` counts, and
+the per-kernel HIP-event times that come with it), writes the last timed frame's canvas if --dump-outputs is given,
+and prints the JSON line. Everything below runs only with --full.
+
+With --full, also on the same JSON line:
   shipped          the shipped direct-lighting configuration (cornell_box.yml's 65 535-row jittered light cache, GI
                    off) at 1920x1080x64: --shipped-steps frames
   gi               the shipped GI configuration (BASELINE configs[4]: 1M photons per map,
@@ -36,8 +41,14 @@ Also on the same JSON line:
   cpu_baseline     the reference's own pthread render_multi on this host's cores, on a
                    bounded sample of the same workload (the same camera at 240x135)
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--gi-steps G] [--scene NAME] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--scene NAME] [--dump-outputs DIR]
+  python bench.py --full [--gpus N] [--steps K] [--warmup W] [--gi-steps G] [--scene NAME] [--no-cpu-baseline]
   torchrun --nproc-per-node N bench.py --gpus N ...
+
+--dump-outputs DIR writes, after the timed frames, what the last timed frame computed: DIR/canvas.npy, float64
+(rows, width, 4), the rows of the gathered canvas that DIR/canvas_rows.npy (float64 row indices) names: every row
+when the canvas fits in 64 MB, otherwise a fixed seeded sample of rows in ascending order. The scene, the seed and
+the sample are fixed, so two builds can be compared canvas for canvas.
 
 With --gpus N > 1 and no torchrun environment, bench.py starts torchrun itself
 (one rank per GPU) before touching the GPU and exits with its status; a
@@ -469,6 +480,35 @@ def scaling_proxy(renderer, shard, height: int, frame_ms_1: float, ns=(2, 4, 8),
     return out
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this much in all
+DUMP_SEED = 0xD0C5
+
+
+def dump_rows(height: int, row_bytes: int, limit: int = DUMP_LIMIT_BYTES):
+    """The canvas rows --dump-outputs writes (ascending): all of them when they fit in `limit` bytes together with
+    their float64 indices and the two .npy headers, otherwise a sample drawn without replacement from a fixed seed."""
+    import numpy as np
+    fit = (limit - 2 * 4096) // (row_bytes + 8)
+    if fit >= height:
+        return np.arange(height)
+    if fit < 1:
+        raise RuntimeError("--dump-outputs: one canvas row (%d bytes) does not fit in %d bytes" % (row_bytes, limit))
+    return np.sort(np.random.RandomState(DUMP_SEED).permutation(height)[:fit])
+
+
+def dump_outputs(out_dir: str, canvas) -> None:
+    """Write the gathered canvas of the last timed frame (a (height, width, 4) float64 device tensor): canvas.npy holds
+    the rows that canvas_rows.npy names."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    rows = dump_rows(canvas.shape[0], canvas[0].numel() * 8)
+    idx = torch.as_tensor(rows, dtype=torch.int64, device=canvas.device)
+    np.save(os.path.join(out_dir, "canvas.npy"), canvas.index_select(0, idx).to(torch.float64).cpu().numpy())
+    np.save(os.path.join(out_dir, "canvas_rows.npy"), rows.astype(np.float64))
+    log("bench: wrote %d of %d canvas rows to %s" % (len(rows), canvas.shape[0], out_dir))
+
+
 def heartbeat(period_s: float = 60.0) -> None:
     """A progress line on stderr every minute while the bench runs (long profiled runs print nothing else)."""
     import threading
@@ -504,7 +544,14 @@ def main():
                     help="skip the GI workload's scaling proxy (about 1.75 GI frames)")
     ap.add_argument("--cpu-all-threads", action="store_true",
                     help="also time the reference's pool at os.cpu_count() threads (256 on the GPU box)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the shipped and GI configurations, the drop-in entry point, the scaling proxy, "
+                         "the rooflines and the CPU baseline (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed frame's canvas to DIR/canvas.npy (and DIR/canvas_rows.npy)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     launch_ranks_if_needed(args)
     heartbeat()
 
@@ -542,7 +589,7 @@ def main():
     # the drop-in entry point, once cold (includes the hiprtc compile of the scene's shadow kernel) and
     # once warm, on device 0 only (rank 0 of a 1-rank run; outside the timed region)
     rm = {}
-    if world == 1 and not args.no_render_multi:
+    if args.full and world == 1 and not args.no_render_multi:
         from fast_ray_tracer_amd.runtime import render_multi_phases
         torch.cuda.init()
         for key in ("render_multi_wall_ms", "render_multi_wall_ms_warm"):
@@ -599,10 +646,14 @@ def main():
     # error flags every frame and fails the render if one is set)
     sync()
     t0 = time.perf_counter()
+    canvas = None
     for _ in range(args.steps):
-        frame(renderer, shard, H)
+        _, canvas = frame(renderer, shard, H)
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, canvas)  # (before the next frame renders into the same memory)
+    del canvas
 
     # one instrumented frame after the timed region: per-kernel HIP-event times on the engine stream and
     # the rays traced per frame (the same every frame: same scene, same seed)
@@ -623,7 +674,7 @@ def main():
     t_max = float(t.item())
     total_rays = float(rays.item())
     proxy = None
-    if world == 1 and not args.no_scaling_proxy:
+    if args.full and world == 1 and not args.no_scaling_proxy:
         proxy = {"headline": scaling_proxy(renderer, shard, H, 1e3 * t_max / args.steps,
                                            batch_samples=args.batch_samples)}
     renderer.close()
@@ -633,7 +684,7 @@ def main():
     # the headline size (each path node draws its own cache rows: statistical parity, tests/test_gpu_stochastic.py and
     # the fixed-seed bit-identity of every shadow stage, tests/test_jit.py) ----
     shipped = None
-    if args.shipped_steps > 0 and args.scene == DEFAULT_SCENE:
+    if args.full and args.shipped_steps > 0 and args.scene == DEFAULT_SCENE:
         sscene = scene_of(SHIPPED_SCENE)
         srend = GpuRenderer(sscene, device=local_rank)
         sshard = torch.zeros((shard_capacity(world, sscene.height), sscene.width, 4), dtype=torch.float64, device="cuda")
@@ -673,7 +724,7 @@ def main():
 
     # ---- GI (configs[4]): fresh photon maps inside every timed frame ----
     gi = None
-    if args.gi_steps > 0:
+    if args.full and args.gi_steps > 0:
         gscene = scene_of(GI_SCENE)
         gr = GpuRenderer(gscene, device=local_rank)
         gshard = torch.zeros((shard_capacity(world, gscene.height), gscene.width, 4), dtype=torch.float64, device="cuda")
@@ -720,8 +771,6 @@ def main():
         ms_per_step = 1e3 * t_max / args.steps
         value = total_rays / t_max / 1e6
         ref_rays = reference_rays(args.scene)
-        roof = frame_roofline(d, kernel_ms, launches, args.scene)
-        roof_shadow = shadow_roofline(d, kernel_ms, launches, args.scene) if launches.get("shadow") else None
         out = {
             "metric": "Mrays/s (primary+shadow+secondary) + wall-clock/frame, 1/2/4/8 GPU",
             "value": round(value, 3),
@@ -768,9 +817,11 @@ def main():
                         "sample pairs left, per 16-node sub-tile), frt_jit_beam (frt_jit_beam_list: the nodes of the "
                         "sub-tile pairs left), each deciding its beam by interval bounds over all its rays; "
                         "frt_jit_shadow walks the rays left one by one (DESIGN.md 3.3)"},
-            "roofline": roof,
-            "roofline_shadow_pass": roof_shadow,
         }
+        if args.full:
+            out["roofline"] = frame_roofline(d, kernel_ms, launches, args.scene)
+            out["roofline_shadow_pass"] = (shadow_roofline(d, kernel_ms, launches, args.scene)
+                                           if launches.get("shadow") else None)
         out.update(rm)
         if shipped is not None:
             out["shipped"] = shipped
@@ -781,7 +832,7 @@ def main():
                              "scaling_proxy); predicted_efficiency = the N=1 frame / (N x the slower rank); the RCCL "
                              "canvas gather (~1 ms per 1920x1080 frame) is not included")
             out["scaling_proxy"] = proxy
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(all_threads=args.cpu_all_threads)
         print(json.dumps(out), flush=True)
     if world > 1:
