@@ -2235,6 +2235,28 @@ static int grow(T** p, int64_t& cap, int64_t need) {
 
 __global__ void k_warm(unsigned* p) { p[threadIdx.x] += 1u; }
 
+// A traversal kernel's dynamic LDS above 64 KiB is asked for by attribute, once per scene handle at upload, for the
+// four kernels of the scene's feature set (frt_scene_upload; wide CSG units only). Returns the first refusal.
+template <int F>
+static hipError_t walk_lds_opt_in_f(int bytes) {
+    const void* kernels[4] = {(const void*)frt::k_trace<F>, (const void*)frt::k_trace_redo<F>,
+                              (const void*)frt::k_shadow<F>, (const void*)frt::k_shadow_redo<F>};
+    for (const void* k : kernels) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+static hipError_t walk_lds_opt_in(int features, int bytes) {
+    switch (features & 3) {
+    case 0: return walk_lds_opt_in_f<0>(bytes);
+    case 1: return walk_lds_opt_in_f<1>(bytes);
+    case 2: return walk_lds_opt_in_f<2>(bytes);
+    default: return walk_lds_opt_in_f<3>(bytes);
+    }
+}
+
 extern "C" {
 
 int frt_device_count(void) {
@@ -3194,10 +3216,26 @@ int frt_scene_upload(const frt_scene* sc, int device, frt_scene_handle** out) {
         S.xf_depth = xf_depth;
         S.features = features;
         h->lds_bytes = (size_t)frt::walk_lds_bytes(list_cap, comp_depth, xf_depth, S.mesh_stack);
-        if (h->lds_bytes > 64 * 1024) {
+        // the block's limit is the device's (160 KiB per workgroup on gfx950, not the 64 KiB of earlier parts): a CSG
+        // unit of 34 entries nested 16 deep needs 68 736 B (tests/golden/scenes/csg_wide34_48.c)
+        int lds_max = 64 * 1024;
+        if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) {
+            (void)hipGetLastError();
+            lds_max = 64 * 1024;
+        }
+        if (h->lds_bytes > (size_t)lds_max) {
             frt_scene_release(h);
             return fail("frt_scene_upload: scene needs " + std::to_string(h->lds_bytes) +
                         " B of LDS per traversal block (CSG lists / nesting too large)");
+        }
+        if (h->lds_bytes > 64 * 1024) {
+            const hipError_t e = walk_lds_opt_in(features, (int)h->lds_bytes);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                frt_scene_release(h);
+                return fail("frt_scene_upload: " + std::to_string(h->lds_bytes) +
+                            " B of LDS per traversal block refused (" + hipGetErrorString(e) + ")");
+            }
         }
     }
     {

@@ -19,6 +19,11 @@ SCENES it:
 Scene assets the scenes load at run time (OBJ meshes, PNG textures) are
 copied as data into tests/golden/assets/ with their relative paths, so the
 tests run on a machine without /root/reference.
+
+A scene whose program is written by this project (source kind "c:<name>", the
+CSG conformance scenes of make_fixture_csg.py) already has its
+tests/golden/scenes/<name>.c: steps 1 and 2 are skipped and step 3 runs on that
+file as it stands.
 """
 from __future__ import annotations
 
@@ -186,6 +191,15 @@ SCENES = {
     "checkered_sphere_dof_square_100": ("scenes/checkered_sphere/checkered_sphere.yml",
                                         {"size": (100, 100), "steps": (4, 4), "jitter": True, "threads": 1,
                                          "aperture": (["SQUARE_APERTURE"], 0.4), "extra_seeds": STOCHASTIC_SEEDS}),
+    # CSG conformance scenes (make_fixture_csg.py writes their main.c; one reference thread, set in the file)
+    "csg_ops_96x64": ("c:csg_ops_96x64", {}),
+    "csg_nested_96x64": ("c:csg_nested_96x64", {}),
+    "csg_ties_64x48": ("c:csg_ties_64x48", {}),
+    "csg_noshadow_glass_64x48": ("c:csg_noshadow_glass_64x48", {}),
+    "csg_unsorted_64x48": ("c:csg_unsorted_64x48", {}),
+    "csg_wide32_48": ("c:csg_wide32_48", {}),
+    "csg_wide34_48": ("c:csg_wide34_48", {}),
+    "csg_nested_nogroup_96x64": ("c:csg_nested_nogroup_96x64", {}),
 }
 FIXTURE_YML = os.path.join(HERE, "yml")
 
@@ -263,39 +277,45 @@ def main(names):
 
     for name in names:
         yml_rel, ov = SCENES[name]
-        yml_path = (os.path.join(FIXTURE_YML, yml_rel[4:]) if yml_rel.startswith("frt:")
-                    else os.path.join(REF_COPY, yml_rel))
-        with open(yml_path) as f:
-            tree = yaml.safe_load(f)
-        for asset in ov.get("extra_assets", []):
-            # fixture data the scene loads at run time (our own files or the reference's scene data):
-            # into tests/golden/assets and the scratch reference copy the reference binary runs in
-            src = os.path.join(assets_dir, asset)
-            if not os.path.exists(src):
-                os.makedirs(os.path.dirname(src), exist_ok=True)
-                shutil.copyfile(os.path.join(REF_COPY, asset), src)
-            dst = os.path.join(REF_COPY, asset)
-            os.makedirs(os.path.dirname(dst), exist_ok=True)
-            shutil.copyfile(src, dst)
-        tree = apply_overrides(copy.deepcopy(tree), name, ov)
-        yml_out = os.path.join(SCRATCH, name + ".yml")
-        with open(yml_out, "w") as f:
-            yaml.safe_dump(tree, f, sort_keys=False)
-        gen = subprocess.run([sys.executable, "yaml_parser/yaml_parser.py", yml_out], cwd=REF_COPY,
-                             capture_output=True, text=True)
-        if gen.returncode != 0:
-            print("codegen failed for", name, gen.stderr[-2000:])
-            continue
         main_c = os.path.join(scenes_dir, name + ".c")
-        with open(main_c, "w") as f:
-            f.write(gen.stdout)
-        for asset in assets_of(gen.stdout):
-            dst = os.path.join(assets_dir, asset)
-            os.makedirs(os.path.dirname(dst), exist_ok=True)
-            shutil.copyfile(os.path.join(REF_COPY, asset), dst)
-            mtl = asset[:-3] + "mtl"
-            if asset.endswith(".obj") and os.path.exists(os.path.join(REF_COPY, mtl)):
-                shutil.copyfile(os.path.join(REF_COPY, mtl), os.path.join(assets_dir, mtl))
+        if yml_rel.startswith("c:"):
+            # the scene program is committed as written (make_fixture_csg.py): no YAML, no codegen
+            if yml_rel[2:] != name or not os.path.exists(main_c):
+                print("no scene program for", name, "(run make_fixture_csg.py)")
+                continue
+        else:
+            yml_path = (os.path.join(FIXTURE_YML, yml_rel[4:]) if yml_rel.startswith("frt:")
+                        else os.path.join(REF_COPY, yml_rel))
+            with open(yml_path) as f:
+                tree = yaml.safe_load(f)
+            for asset in ov.get("extra_assets", []):
+                # fixture data the scene loads at run time (our own files or the reference's scene data):
+                # into tests/golden/assets and the scratch reference copy the reference binary runs in
+                src = os.path.join(assets_dir, asset)
+                if not os.path.exists(src):
+                    os.makedirs(os.path.dirname(src), exist_ok=True)
+                    shutil.copyfile(os.path.join(REF_COPY, asset), src)
+                dst = os.path.join(REF_COPY, asset)
+                os.makedirs(os.path.dirname(dst), exist_ok=True)
+                shutil.copyfile(src, dst)
+            tree = apply_overrides(copy.deepcopy(tree), name, ov)
+            yml_out = os.path.join(SCRATCH, name + ".yml")
+            with open(yml_out, "w") as f:
+                yaml.safe_dump(tree, f, sort_keys=False)
+            gen = subprocess.run([sys.executable, "yaml_parser/yaml_parser.py", yml_out], cwd=REF_COPY,
+                                 capture_output=True, text=True)
+            if gen.returncode != 0:
+                print("codegen failed for", name, gen.stderr[-2000:])
+                continue
+            with open(main_c, "w") as f:
+                f.write(gen.stdout)
+            for asset in assets_of(gen.stdout):
+                dst = os.path.join(assets_dir, asset)
+                os.makedirs(os.path.dirname(dst), exist_ok=True)
+                shutil.copyfile(os.path.join(REF_COPY, asset), dst)
+                mtl = asset[:-3] + "mtl"
+                if asset.endswith(".obj") and os.path.exists(os.path.join(REF_COPY, mtl)):
+                    shutil.copyfile(os.path.join(REF_COPY, mtl), os.path.join(assets_dir, mtl))
         entry = {"yaml": yml_rel, "overrides": {k: v for k, v in ov.items()}}
         if ov.get("no_golden"):
             index[name] = entry
@@ -329,6 +349,8 @@ def main(names):
             "ppm_sha256": sha256(out_base + ".ppm"), "png_sha256": sha256(out_base + ".png"),
             "canvas_sum": [float(x) for x in canvas.reshape(-1, 3).sum(axis=0)],
         })
+        if yml_rel.startswith("c:"):
+            del entry["ref_render_multi_seconds"]  # (a wall time: these entries regenerate byte for byte)
         arrays = {"canvas": canvas}
         if ov.get("extra_seeds"):
             # further independent reference renders (drand48 / rand() re-seeded by the harness)

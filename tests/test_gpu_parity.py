@@ -80,6 +80,20 @@ def test_gpu_full_frame_determinism_and_split_invariance(built):
     assert np.isfinite(full).all()
 
 
+@pytest.mark.parametrize("name", ["csg_nested_96x64", "csg_unsorted_64x48"])
+def test_csg_scenes_split_and_batch_invariance(built, name):
+    """CSG units through the generated kernels (csg_nested_96x64) and through the generic list walk
+    (csg_unsorted_64x48): the 2-way and 3-way row interleave and batches of 2^12 samples (tiles of 64 nodes cut
+    in the middle of a unit's pixels) leave every bit of the full frame unchanged."""
+    r = renderer(name)
+    full = r.render()
+    assert np.isfinite(full).all() and full[:, :, :3].max() > 0
+    for n in (2, 3):
+        for k in range(n):
+            assert np.array_equal(full[k::n], r.render(k, None, n)), (n, k)
+    assert np.array_equal(full, r.render(batch_samples=1 << 12))
+
+
 def test_drop_in_executable_renders_reference_ppm(built, tmp_path):
     """The unmodified generated main.c, linked against libfrt_host, renders on the
     GPU through render_multi and writes the reference's PPM bytes at full size."""
@@ -360,7 +374,8 @@ def _render_frame_env(name, env, **kw):
         r.close()
 
 
-@pytest.mark.parametrize("name", ["cornell_direct_64_4x4", "reflect_refract_test_150", "patterns_160x80"])
+@pytest.mark.parametrize("name", ["cornell_direct_64_4x4", "reflect_refract_test_150", "patterns_160x80",
+                                  "csg_noshadow_glass_64x48"])
 def test_lazy_ambient_equals_stored_surface(built, name):
     """Without GI the path nodes no light sample reaches are not written by k_shade: k_combine computes their
     ambient terms where it would read them (frt_engine.hip ambient_node). The canvas must equal the one with
@@ -437,9 +452,11 @@ def test_row_sorted_shading_equals_list_order(built, name, rows):
     plain = _render_env(name, {"FRT_SHADE_SORT": "0"}, **kw)
     assert np.isfinite(sorted_).all() and sorted_[:, :, :3].max() > 0
     assert np.array_equal(sorted_, plain)
-    # without GI the row-ordered shading reads staged records and writes its triples in row order (k_lit_stage,
-    # combine through spos); FRT_SHADE_STAGE=0 reads the node records in row order as round 5 did
-    for mode in ("0", "2"):  # (2: the node records read in row order, the triples still written in row order)
+    # the row-ordered shading's three modes (frt_engine.hip FRT_SHADE_STAGE), each set explicitly: 2 (the default)
+    # reads the node records in row order and writes its triples in row order (combine through spos); 1 also stages
+    # the records in list order first (k_lit_stage) and shades from the staged copies; 0 reads and writes by node,
+    # as round 5 did
+    for mode in ("0", "1", "2"):
         other = _render_env(name, {"FRT_SHADE_SORT": "1", "FRT_SHADE_STAGE": mode}, **kw)
         assert np.array_equal(other, plain), mode
 
@@ -552,7 +569,8 @@ def test_render_multi_canvas_is_pinned_and_pooled(built):
 
 @pytest.mark.parametrize("name,rows", [("reflect_refract_test_150", None), ("cornell_direct_64_4x4", None),
                                        ("cornell_gi_24", None), ("cornell_shipped_48_4x4", None),
-                                       ("cornell_direct_1920x1080_8x8", (700, 708))])
+                                       ("cornell_direct_1920x1080_8x8", (700, 708)),
+                                       ("csg_noshadow_glass_64x48", None)])
 def test_queue_order_equals_segment_order(built, name, rows):
     """The secondary levels' nodes in parent order (FRT_QUEUE_SORT): 2 (default) children at fixed slots n * slot +
     node compacted in order, 1 the segmented queue radix-sorted by (slot, parent), 0 the segments' append order.

@@ -15,7 +15,16 @@ from conftest import GOLDEN, load_scene
 SCENES = sorted(f[:-2] for f in os.listdir(os.path.join(GOLDEN, "scenes")) if f.endswith(".c"))
 # scenes whose tree the generator must accept (CSG units of sorted leaves, <= 512 nodes)
 ELIGIBLE = {"cornell_direct_800_4x4", "cornell_direct_64_4x4", "checkered_sphere_200", "reflect_refract_160x80",
-            "reflect_refract_test_150", "shadow_glamour_150x60", "test_scene_120", "cornell_gi_24"}
+            "reflect_refract_test_150", "shadow_glamour_150x60", "test_scene_120", "cornell_gi_24",
+            "csg_ops_96x64", "csg_nested_96x64", "csg_ties_64x48", "csg_noshadow_glass_64x48", "csg_wide32_48",
+            "csg_nested_nogroup_96x64"}
+# the CSG conformance scenes (tests/golden/make_fixture_csg.py) the generator accepts, and the two it must refuse
+CSG_ELIGIBLE = ["csg_ops_96x64", "csg_nested_96x64", "csg_ties_64x48", "csg_noshadow_glass_64x48", "csg_wide32_48"]
+# those with a closest-hit kernel of their own (frt_jit.hip: none for a group inside a unit, csg_nested_96x64, and
+# the engine uses none where a refractive index is not one, csg_noshadow_glass_64x48); csg_nested_nogroup_96x64 is
+# csg_nested_96x64 without its group unit
+CSG_CLOSEST = ["csg_ops_96x64", "csg_ties_64x48", "csg_wide32_48", "csg_nested_nogroup_96x64"]
+CSG_REFUSED = {"csg_unsorted_64x48": "holds a leaf with an unsorted list", "csg_wide34_48": "has too many entries"}
 
 
 @pytest.mark.parametrize("name", SCENES)
@@ -28,6 +37,25 @@ def test_jit_source_compiles(built, name):
         assert "frt_jit_shadow" in src
     else:
         assert rc in (0, 1)
+
+
+@pytest.mark.parametrize("name", sorted(CSG_REFUSED))
+def test_jit_refuses_unsorted_leaves_and_wide_units(built, name):
+    """A CSG unit with a cylinder, cone or torus leaf (lists not sorted by t), or with more than kMaxSlots = 32
+    entries (17 cubes), is not written with slots: jit_check returns 1 and names the reason."""
+    from fast_ray_tracer_amd.runtime import jit_check
+    rc, log, _ = jit_check(load_scene(name))
+    assert rc == 1, log
+    assert CSG_REFUSED[name] in log, log
+
+
+def test_jit_accepts_a_unit_of_exactly_32_entries(built):
+    """16 cubes in one left-deep UNION chain are 32 entries, the limit: accepted, with slots t0 .. t31."""
+    import re
+    from fast_ray_tracer_amd.runtime import jit_check
+    rc, log, src = jit_check(load_scene("csg_wide32_48"))
+    assert rc == 0, log
+    assert re.search(r"\bt31\b", src) and not re.search(r"\bt32\b", src)
 
 
 def _render(name, jit, beam=True, **kw):
@@ -53,13 +81,16 @@ def _render(name, jit, beam=True, **kw):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["cornell_direct_64_4x4", "reflect_refract_test_150", "shadow_glamour_150x60",
-                                  "group_test_150x50", "test_scene_120", "cornell_shipped_48_4x4"])
+                                  "group_test_150x50", "test_scene_120", "cornell_shipped_48_4x4"]
+                         + CSG_ELIGIBLE + sorted(CSG_REFUSED))
 def test_jit_equals_generic_walk(built, name):
     img_j, st_j = _render(name, True)
     img_g, st_g = _render(name, False)
     assert st_g.shadow_jit == 0
     if name in ELIGIBLE:
         assert st_j.shadow_jit == 1
+    if name in CSG_REFUSED:  # (FRT_JIT=1 and a refused tree: the generic walk ran)
+        assert st_j.shadow_jit == 0
     assert np.array_equal(img_j, img_g)
 
 
@@ -74,7 +105,7 @@ def test_jit_equals_generic_walk_on_benchmark_rows(built):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["cornell_direct_64_4x4", "cornell_shipped_48_4x4", "reflect_refract_test_150",
-                                  "test_scene_120", "checkered_sphere_200"])
+                                  "test_scene_120", "checkered_sphere_200"] + CSG_ELIGIBLE)
 def test_pair_kernel_equals_per_ray_walk(built, name):
     """frt_jit_beam decides whole (node, light) pairs; the counts it writes must equal what the per-ray
     walk gives for every ray of the pair: the canvas with and without it, bit for bit."""
@@ -126,7 +157,7 @@ print("STATS", d["shadow_jit"], d["shadow_tile_pairs"], d["shadow_sub_pairs"])
 """
 
 
-def _render_env_process(name, env, out, **kw):
+def _render_env_process(name, env, out, want_stderr=False, **kw):
     """Render in a fresh process (the tile size and sub-part count are read once per process)."""
     import subprocess
     import sys
@@ -139,12 +170,14 @@ def _render_env_process(name, env, out, **kw):
                        env=penv, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     stats = [ln.split()[1:] for ln in p.stdout.splitlines() if ln.startswith("STATS")][-1]
+    if want_stderr:
+        return np.load(str(out)), [int(x) for x in stats], p.stderr
     return np.load(str(out)), [int(x) for x in stats]
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["cornell_direct_64_4x4", "reflect_refract_test_150", "test_scene_120",
-                                  "cornell_shipped_48_4x4"])
+                                  "cornell_shipped_48_4x4", "csg_nested_96x64", "csg_ties_64x48"])
 def test_tile_and_sub_part_kernels_equal_generic_walk(built, name, tmp_path):
     """The tile pair kernel (frt_jit_tile: runs of consecutive path nodes from their origin box), the sub-part pass
     after it (frt_jit_sub: the tile pairs left mixed, their parts split into sub-parts; 16 single samples of the
@@ -173,15 +206,30 @@ def test_tile_and_sub_part_kernels_equal_generic_walk(built, name, tmp_path):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["cornell_direct_64_4x4", "checkered_torus_120", "checkered_cylinder_120", "group_test_150x50",
                                   "teapot_low_100", "checkered_sphere_dof_100", "patterns_160x80", "cornell_gi_16",
-                                  "test_scene_120", "bump_map_100"])
+                                  "test_scene_120", "bump_map_100"] + CSG_ELIGIBLE + sorted(CSG_REFUSED)
+                         + ["csg_nested_nogroup_96x64"])
 def test_jit_closest_hit_equals_generic_walk(built, name, tmp_path):
     """The scene-specialised closest-hit kernel (frt_jit_trace: binary32 intervals, the winner's t from its own leaf
     in binary64, the rays it cannot settle handed to the generic walk by k_trace_redo) against k_trace for every
     ray (FRT_JIT_TRACE=0): the canvases are bit-identical (camera rays, reflected rays and, on cornell_gi_16,
-    final-gather rays)."""
+    final-gather rays). On the CSG scenes that have such a kernel (CSG_CLOSEST) it must have run and settled rays
+    itself; on csg_nested_96x64 and csg_noshadow_glass_64x48 both sides are k_trace by design."""
     ref, _ = _render_env_process(name, {"FRT_JIT_TRACE": "0"}, tmp_path / "g.npy")
-    img, _ = _render_env_process(name, {}, tmp_path / "j.npy")
+    env = {"FRT_JIT": "1"} if name in CSG_REFUSED else {}
+    if name in CSG_CLOSEST:  # (the engine's own per-launch report on stderr; it synchronises, nothing else changes)
+        env["FRT_JIT_TRACE_STATS"] = "1"
+    img, st, err = _render_env_process(name, env, tmp_path / "j.npy", want_stderr=True)
     assert np.array_equal(img, ref), name
+    if name in CSG_REFUSED:
+        assert st[0] == 0, st
+    if name in CSG_CLOSEST:
+        # frt_jit_trace ran on the CSG trees and settled rays itself: not every ray went on to k_trace_redo
+        import re
+        launches = [(int(a), int(b)) for a, b in
+                    re.findall(r"frt_jit_trace level \d+: (\d+) rays, (\d+) to the generic walk", err)]
+        rays, redo = sum(a for a, _ in launches), sum(b for _, b in launches)
+        print(f"{name}: frt_jit_trace {rays} rays in {len(launches)} launches, {redo} to the generic walk")
+        assert launches and redo < rays, (name, launches)
 
 
 @pytest.mark.gpu
@@ -238,7 +286,7 @@ def test_small_levels_skip_beam_stages_bit_identical(built, tmp_path):
 @pytest.mark.parametrize("name", ["cornell_direct_64_4x4", "patterns_160x80", "teapot_low_100", "nave_120x150_4x4",
                                   "checkered_torus_120", "reflect_refract_test_150", "bounding_boxes_100x125_4x4",
                                   "area_light_test_100", "checkered_sphere_dof_100", "cornell_gi_24",
-                                  "cornell_shipped_48_4x4"])
+                                  "cornell_shipped_48_4x4", "csg_ops_96x64", "csg_unsorted_64x48"])
 def test_goldens_under_the_production_default(built, name, tmp_path):
     """The test session walks every level through the beam stages (conftest: FRT_JIT_MIN_PAIRS=0); the shipped default
     (unset: levels under 2^18 (node, part) pairs walk their rays one by one, i.e. every level of these small scenes)
