@@ -44,6 +44,7 @@
 #include "frt_device.h"
 #include "frt_jit.h"
 #include "frt_shade.hpp"
+#include "frt_shade32.hpp"
 #include "frt_shadow.hpp"
 #include "frt_jit_rt.hpp"
 #include "frt_camera.hpp"
@@ -920,6 +921,123 @@ __device__ __forceinline__ void shade_node(const DevScene& S, const Batch& B, co
     out[3] = out[7] = out[11] = 0.0;
 }
 
+// The fast shading mode (frt_frame_params.precision = FRT_PRECISION_FAST32): shade_node with the light-point loop in
+// binary32 (frt_shade32.hpp: what is binary32, the error model, the lanes that fall back to binary64 per point).
+// Everything per node and per light stays binary64 and as shade_node writes it: inten, the ambient terms, the
+// factored tail Kd I sum(l.n), Ks I sum(b) + (1 - Ks) I sum(F b), scaling, the sums over the lights.
+// F: every light's points as binary32 offsets from the light's centroid (the index of light_points, 3 floats per
+// point) and the centroids (3 doubles per light), built when a handle renders its first fast frame (ensure_light32).
+struct Light32 {
+    const float* __restrict__ off;
+    const double* __restrict__ cent;
+};
+__device__ __forceinline__ void shade_node32(const DevScene& S, const Batch& B, const Light32& F, const NodeRec& nr,
+                                             int64_t i, const int32_t* __restrict__ counts, double* out, int32_t c0) {
+    double sA[3] = {0, 0, 0}, sD[3] = {0, 0, 0}, sS[3] = {0, 0, 0};
+    if (S.cfg.include_direct) {
+        for (int li = 0; li < S.num_lights; ++li) {
+            const frt_light& L = S.lights[li];
+            const int32_t cnt = c0 >= 0 ? c0 : counts[i * S.num_lights + li];
+            double inten;
+            if (L.type == FRT_AREA_LIGHT || L.type == FRT_CIRCLE_LIGHT) {
+                inten = (double)cnt / (double)L.num_samples;  // light.c:229-242
+            } else {
+                inten = cnt ? 1.0 : 0.0;  // light.c:245-251
+            }
+            double amb[3], cA[3] = {0, 0, 0}, cD[3] = {0, 0, 0}, cS[3] = {0, 0, 0};
+            for (int k = 0; k < 3; ++k) amb[k] = nr.Ka[k] * L.intensity[k];
+            if (!feq(inten, 0.0) && (S.cfg.include_diffuse || S.cfg.include_spec_highlight)) {
+                Point64 Q;
+                for (int k = 0; k < 3; ++k) {
+                    Q.base[k] = F.cent[3 * li + k] - nr.over_point[k];
+                    Q.n[k] = nr.normalv[k];
+                    Q.e[k] = nr.eyev[k];
+                }
+                Q.ned = S.cfg.include_spec_highlight ? dot3(nr.normalv, nr.eyev) : 0.0;
+                Q.ee = dot3(nr.eyev, nr.eyev);
+                Q.ns = nr.Ns;
+                Q.cdist = (nr.Ns + 2) * 0.5 * k1Pi;
+                // (shade_node's specular tail constant, from the same binary64 values)
+                float skip_c = __builtin_huge_valf();
+                if (FRT_SHADE_SKIP && S.cfg.include_diffuse && S.cfg.include_spec_highlight && Q.ns >= 2.0 &&
+                    Q.ns <= 4096.0 && Q.ned > 0x1p-100) {
+                    double rk = 1.0;
+                    for (int k = 0; k < 3; ++k) rk = fmin(rk, nr.Kd[k] / (fabs(nr.Ks[k]) + fabs(1.0 - nr.Ks[k])));
+                    if (rk > 0x1p-100) skip_c = __log2f((float)(Q.cdist / (rk * Q.ned))) + 66.0f;
+                }
+                const Point32 P = point32_of(Q, skip_c, S.cfg.include_diffuse != 0, S.cfg.include_spec_highlight != 0);
+                ShadeSums sums = {0.0, 0.0, 0.0};
+                const int ns = L.num_samples;
+                const float* row0 = F.off + L.points;
+                // a wave-uniform row through the scalar cache, the next point's loads ahead of this one's arithmetic
+                // (shade_node's uniform_points)
+                using const_pts = const __attribute__((address_space(4))) float*;
+                auto uniform_points = [&](const float* up) {
+                    const const_pts sp = (const_pts)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(
+                                                          (int)(uint32_t)(uint64_t)up)) |
+                                                      ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(
+                                                           (int)(uint32_t)((uint64_t)up >> 32))
+                                                       << 32));
+                    float a[3] = {sp[0], sp[1], sp[2]};
+                    for (int p = 0; p < ns; ++p) {
+                        const float lp[3] = {a[0], a[1], a[2]};
+                        const const_pts q = sp + 3 * min(p + 1, ns - 1);
+                        a[0] = q[0];
+                        a[1] = q[1];
+                        a[2] = q[2];
+                        point_term32(P, Q, lp, sums);
+                    }
+                };
+                const int row = L.rows <= 1 ? 0 : light_row(L, B.seed, nr.key, li, 1);
+                const int ra = __builtin_amdgcn_readfirstlane(row);
+                if (L.rows <= 1) {
+                    uniform_points(row0);
+                } else if (__ballot(row != ra) == 0ull) {
+                    uniform_points(row0 + 3 * (int64_t)ra * ns);  // (the wave shares its row: the same points per lane)
+                } else {
+                    // the node's own row (per lane), each point's loads two points ahead of its arithmetic
+                    const float* pts = row0 + 3 * (int64_t)row * ns;
+                    float a[3] = {pts[0], pts[1], pts[2]};
+                    const float* q1 = pts + 3 * min(1, ns - 1);
+                    float b[3] = {q1[0], q1[1], q1[2]};
+                    for (int p = 0; p < ns; ++p) {
+                        const float lp[3] = {a[0], a[1], a[2]};
+                        a[0] = b[0];
+                        a[1] = b[1];
+                        a[2] = b[2];
+                        const float* q = pts + 3 * min(p + 2, ns - 1);
+                        b[0] = q[0];
+                        b[1] = q[1];
+                        b[2] = q[2];
+                        point_term32(P, Q, lp, sums);
+                    }
+                }
+                const double scaling = inten / (double)L.num_samples;
+                for (int k = 0; k < 3; ++k) {
+                    const double dacc = nr.Kd[k] * L.intensity[k] * sums.ldn;
+                    const double sacc =
+                        nr.Ks[k] * L.intensity[k] * sums.b + (1.0 - nr.Ks[k]) * L.intensity[k] * sums.fb;
+                    cD[k] = (0.0 + dacc) * scaling;
+                    cS[k] = (0.0 + sacc) * scaling;
+                }
+            }
+            if (S.cfg.include_ambient)
+                for (int k = 0; k < 3; ++k) cA[k] = 0.0 + amb[k];
+            for (int k = 0; k < 3; ++k) {
+                sA[k] += cA[k];
+                sD[k] += cD[k];
+                sS[k] += cS[k];
+            }
+        }
+    }
+    for (int k = 0; k < 3; ++k) {
+        out[k] = sA[k];
+        out[4 + k] = sD[k];
+        out[8 + k] = sS[k];
+    }
+    out[3] = out[7] = out[11] = 0.0;
+}
+
 // the node's shading loops over light points: some light reaches it (a non-zero unshadowed count:
 // lighting_microfacet's `if (!feq(intensity, 0))`, renderer.c:909) and diffuse or highlights are on
 __device__ __forceinline__ bool shade_heavy(const DevScene& S, const int32_t* __restrict__ counts, int64_t i) {
@@ -1117,13 +1235,15 @@ __global__ void __launch_bounds__(kBlock) k_lit_stage(DevScene S, Batch B, NodeC
 #define FRT_SHADE_WAVES 4
 #endif
 // (kRows: the list in light-row order, a multi-row light's row staged per wave in LDS)
-template <bool kRows>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(FRT_SHADE_WAVES, 8))) k_shade_lit(DevScene S, Batch B, NodeCols rec,
-                                                      const int32_t* __restrict__ counts, Cols<Tri9> surface,
-                                                      const uint32_t* __restrict__ lit,
-                                                      const unsigned* __restrict__ lcount, uint32_t segcap,
-                                                      const uint32_t* __restrict__ flat,
-                                                      const LitStage* __restrict__ stage, uint32_t* __restrict__ spos) {
+// (kFast32: the body of k_shade_lit32, the light-point loops in binary32 from F; everything else is shared)
+template <bool kRows, bool kFast32>
+__device__ __forceinline__ void shade_lit_body(const DevScene& S, const Batch& B, const NodeCols& rec,
+                                               const int32_t* __restrict__ counts, Cols<Tri9> surface,
+                                               const uint32_t* __restrict__ lit,
+                                               const unsigned* __restrict__ lcount, uint32_t segcap,
+                                               const uint32_t* __restrict__ flat,
+                                               const LitStage* __restrict__ stage, uint32_t* __restrict__ spos,
+                                               const Light32& F) {
     const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
     // the listed total: every lane reads one segment's count (uniform per wave)
     const int lane = threadIdx.x & 63;
@@ -1196,7 +1316,9 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(FRT
 #ifndef FRT_SHADE_LDS_ROWS
 #define FRT_SHADE_LDS_ROWS 0
 #endif
-    if (kRows && FRT_SHADE_LDS_ROWS) {
+    if constexpr (kFast32) {
+        shade_node32(S, B, F, nr, i, counts, out, c0);
+    } else if (kRows && FRT_SHADE_LDS_ROWS) {
         __shared__ double lds_rows[kBlock / 64][3 * kLdsPoints];  // (a multi-row light's row per wave, 3 KB)
         shade_node(S, B, nr, i, counts, out, lds_rows[threadIdx.x >> 6], c0);
     } else {
@@ -1214,6 +1336,28 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(FRT
         return;
     }
     tri_store(surface, i, out);
+}
+
+template <bool kRows>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(FRT_SHADE_WAVES, 8))) k_shade_lit(DevScene S, Batch B, NodeCols rec,
+                                                      const int32_t* __restrict__ counts, Cols<Tri9> surface,
+                                                      const uint32_t* __restrict__ lit,
+                                                      const unsigned* __restrict__ lcount, uint32_t segcap,
+                                                      const uint32_t* __restrict__ flat,
+                                                      const LitStage* __restrict__ stage, uint32_t* __restrict__ spos) {
+    shade_lit_body<kRows, false>(S, B, rec, counts, surface, lit, lcount, segcap, flat, stage, spos, Light32{});
+}
+
+// k_shade_lit in the fast shading mode: the same lists, records and output places, shade_node32 per lane
+template <bool kRows>
+__global__ void __launch_bounds__(kBlock) k_shade_lit32(DevScene S, Batch B, NodeCols rec,
+                                                        const int32_t* __restrict__ counts, Cols<Tri9> surface,
+                                                        const uint32_t* __restrict__ lit,
+                                                        const unsigned* __restrict__ lcount, uint32_t segcap,
+                                                        const uint32_t* __restrict__ flat,
+                                                        const LitStage* __restrict__ stage, uint32_t* __restrict__ spos,
+                                                        Light32 F) {
+    shade_lit_body<kRows, true>(S, B, rec, counts, surface, lit, lcount, segcap, flat, stage, spos, F);
 }
 
 // bottom-up combine of one node (shade_hit's specular block, renderer.c:773-822): its A, D, S triples into col
@@ -2107,6 +2251,10 @@ struct frt_scene_handle {
     int64_t lit_flat_cap = 0;
     frt::LitStage* lit_stage = nullptr;  // (k_lit_stage's records, FRT_SHADE_STAGE)
     int64_t lit_stage_cap = 0;
+    // the fast shading mode: this frame's mode, and the lights' points as binary32 offsets from their centroids
+    // (ensure_light32: built by the handle's first fast frame, so a parity-only handle never holds them)
+    bool fast32 = false;
+    frt::Light32 light32{nullptr, nullptr};
     int queue_sort = 2;                 // a level's queue in parent order (FRT_QUEUE_SORT: 2 dense, 1 sorted, 0 off)
     int queue_sort_shift = 0;           // (FRT_QUEUE_SORT_SHIFT)
     uint32_t* qsort = nullptr;          // (its keys, their alternate buffer and the storage slots, 3 words per entry)
@@ -2853,6 +3001,138 @@ int64_t frt_math_selftest(int64_t n, uint64_t seed) {
     hip_ignore(hipFree(bad));
     return ok ? (int64_t)h : -1;
 }
+
+// Diagnostics: the fast mode's binary32 light-point term (point_term32, frt_shade32.hpp) against the binary64 term on
+// one point per lane. Lane i: over_point o and the light's centroid c with components in [-4.6, 4.6] and [-4, 4],
+// the point's offset in [-0.5, 0.5]^3 (so |o|, |point| <= 8), o moved 2 along x towards the origin where |diff| < 1;
+// unit normal n and eye e; Ns = {0, 1, 2.5, 10, 200, 1000, 5000}[i mod 7]. Of every 8 lanes, 2 get n.l = eps (n built
+// from a vector across l plus eps l, eps in {1e-30, 1e-20, 1e-10, 1e-6, 1e-3, -1e-12, -1e-6}), 1 gets n.e = eps
+// (eps > 0 of that list), 3 an eye on the normal's side, 2 any eye. res[0]: lanes whose binary32 sums are not finite
+// while the binary64 ones are, plus lanes whose l.n is off by more than 32 * 2^-24; res[1..3] (bit patterns of
+// non-negative doubles, atomicMax): the worst |b32 - b64| / b64 over the lanes with l.n >= 2^-16 and b64 >= 2^-100
+// (closer to l.n = 0 the two evaluations may disagree on whether the point contributes at all), the same over their
+// Ns <= 200 lanes, the worst |l.n| difference; res[4]: the lanes in res[1].
+__global__ void k_shade32_selftest(int64_t n, uint64_t seed, unsigned long long* res) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;  // (whole waves: n is a multiple of 64)
+    uint64_t ctr = 0;
+    auto u01 = [&]() {
+        const uint64_t h = frt::mix64(seed ^ frt::mix64((uint64_t)i * 64 + (ctr++) + 0x9e3779b97f4a7c15ULL));
+        return (double)(h >> 11) * 0x1.0p-53;
+    };
+    auto unit = [&](double* v) {  // (a direction from the cube, rejected outside the ball and near its centre)
+        for (int t = 0; t < 16; ++t) {
+            for (int k = 0; k < 3; ++k) v[k] = 2.0 * u01() - 1.0;
+            const double m2 = frt::dot3(v, v);
+            if (m2 <= 1.0 && m2 >= 0.01) break;
+        }
+        double m2 = frt::dot3(v, v);
+        if (!(m2 <= 1.0 && m2 >= 0.01)) v[0] = 1.0, v[1] = v[2] = 0.0, m2 = 1.0;
+        const double inv = 1.0 / sqrt(m2);
+        for (int k = 0; k < 3; ++k) v[k] *= inv;
+    };
+    auto across = [&](const double* a, double eps, double* r) {  // unit r with r.a = eps (to rounding), a unit
+        double t[3], x[3];
+        unit(t);
+        frt::cross3(a, t, x);
+        if (frt::dot3(x, x) < 1e-4) {
+            const double alt[3] = {a[1], a[2], a[0] + 0.5};
+            frt::cross3(a, alt, x);
+        }
+        const double inv = 1.0 / sqrt(frt::dot3(x, x));
+        for (int k = 0; k < 3; ++k) r[k] = x[k] * inv + eps * a[k];
+        const double rn = 1.0 / sqrt(frt::dot3(r, r));
+        for (int k = 0; k < 3; ++k) r[k] *= rn;
+    };
+    double o[3], c[3], lp[3];
+    float off[3];
+    for (int k = 0; k < 3; ++k) {
+        o[k] = 9.2 * u01() - 4.6;
+        c[k] = 8.0 * u01() - 4.0;
+        off[k] = (float)(u01() - 0.5);
+        lp[k] = c[k] + (double)off[k];
+    }
+    {
+        const double d[3] = {lp[0] - o[0], lp[1] - o[1], lp[2] - o[2]};
+        if (frt::dot3(d, d) < 1.0) o[0] = lp[0] + (lp[0] > 0.0 ? -2.0 : 2.0);
+    }
+    double l[3] = {lp[0] - o[0], lp[1] - o[1], lp[2] - o[2]};
+    {
+        const double inv = 1.0 / sqrt(frt::dot3(l, l));
+        for (int k = 0; k < 3; ++k) l[k] *= inv;
+    }
+    const double eps_list[7] = {1e-30, 1e-20, 1e-10, 1e-6, 1e-3, -1e-12, -1e-6};
+    const int kind = (int)(i & 7), pick = (int)((i >> 3) % 7);
+    frt::Point64 Q;
+    if (kind < 2)
+        across(l, eps_list[pick], Q.n);
+    else
+        unit(Q.n);
+    if (kind == 2) {
+        across(Q.n, eps_list[pick % 5], Q.e);
+    } else {
+        unit(Q.e);
+        if (kind < 6 && frt::dot3(Q.n, Q.e) < 0.0)
+            for (int k = 0; k < 3; ++k) Q.e[k] = -Q.e[k];
+    }
+    const double ns_list[7] = {0.0, 1.0, 2.5, 10.0, 200.0, 1000.0, 5000.0};
+    Q.ns = ns_list[i % 7];
+    Q.cdist = (Q.ns + 2) * 0.5 * frt::k1Pi;
+    Q.ned = frt::dot3(Q.n, Q.e);
+    Q.ee = frt::dot3(Q.e, Q.e);
+    for (int k = 0; k < 3; ++k) Q.base[k] = c[k] - o[k];
+    const frt::Point32 P = frt::point32_of(Q, __builtin_huge_valf(), true, true);
+    frt::ShadeSums s32 = {0.0, 0.0, 0.0}, s64 = {0.0, 0.0, 0.0};
+    frt::point_term32(P, Q, off, s32);
+    frt::Point64 R = Q;  // (the binary64 term on the point itself: diff = lp - o)
+    for (int k = 0; k < 3; ++k) R.base[k] = lp[k] - o[k];
+    const double zero[3] = {0.0, 0.0, 0.0};
+    frt::point_term64(R, zero, true, true, s64);
+    const bool fin64 = __builtin_isfinite(s64.ldn) && __builtin_isfinite(s64.b) && __builtin_isfinite(s64.fb);
+    const bool fin32 = __builtin_isfinite(s32.ldn) && __builtin_isfinite(s32.b) && __builtin_isfinite(s32.fb);
+    unsigned long long bad = 0;
+    if (fin64 && !fin32) bad++;
+    const double dl = fabs(s32.ldn - s64.ldn);
+    if (fin64 && fin32 && !(dl <= 32.0 * 0x1p-24)) bad++;
+    if (bad) atomicAdd(res, bad);
+    auto put_max = [&](int slot, double v) {
+        const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+        if (b > res[slot]) atomicMax(res + slot, b);
+    };
+    if (fin64 && fin32) {
+        put_max(3, dl);
+        if (s64.ldn >= 0x1p-16 && s64.b >= 0x1p-100) {
+            const double rel = fabs(s32.b - s64.b) / s64.b;
+            put_max(1, rel);
+            if (Q.ns <= 200.0) put_max(2, rel);
+            atomicAdd(res + 4, 1ull);
+        }
+    }
+}
+
+// out[0] the worst relative deviation of the specular factor over the lanes away from l.n = 0, out[1] the same at
+// Ns <= 200, out[2] the worst absolute l.n deviation, out[3] the lanes behind out[0] (min(nout, 4) written)
+int64_t frt_shade32_selftest(int64_t n, uint64_t seed, double* out, int nout) {
+    n = (std::max<int64_t>(n, 64) + 63) / 64 * 64;
+    unsigned long long* res = nullptr;
+    unsigned long long h[5] = {0, 0, 0, 0, 0};
+    if (hipMalloc((void**)&res, sizeof(h)) != hipSuccess) return -1;
+    bool ok = hipMemset(res, 0, sizeof(h)) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(k_shade32_selftest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, n, seed, res);
+        ok = hipGetLastError() == hipSuccess && hipMemcpy(h, res, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    hip_ignore(hipFree(res));
+    if (!ok) return -1;
+    for (int k = 0; k < nout && k < 4 && out != nullptr; ++k) {
+        double v;
+        std::memcpy(&v, &h[k + 1], sizeof(v));
+        out[k] = k == 3 ? (double)h[4] : v;
+    }
+    return (int64_t)h[0];
+}
+
+size_t frt_frame_params_size(void) { return sizeof(frt_frame_params); }
 
 const char* frt_last_error(void) { return g_last_error.c_str(); }
 
@@ -4723,6 +5003,61 @@ static void dump_walk_stats(frt_scene_handle* h) {
 
 static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* dev_out, frt_frame_stats* st);
 
+// The frame's shading precision: the params' when they name one, else FRT_PRECISION (read per frame), else parity.
+// Sets h->fast32. An unknown value is refused, and so is a fast frame with the shading split off (FRT_SHADE_SPLIT=0
+// shades every node in k_shade, which has no binary32 form): nothing renders parity under the name of fast32.
+static int frame_precision(frt_scene_handle* h, const frt_frame_params* P) {
+    int p = P->precision;
+    if (p == FRT_PRECISION_DEFAULT) {
+        const char* e = std::getenv("FRT_PRECISION");
+        if (e == nullptr || *e == '\0' || std::strcmp(e, "parity") == 0)
+            p = FRT_PRECISION_PARITY;
+        else if (std::strcmp(e, "fast32") == 0)
+            p = FRT_PRECISION_FAST32;
+        else
+            return fail(std::string("FRT_PRECISION=") + e + " is not supported (parity or fast32)");
+    }
+    if (p != FRT_PRECISION_PARITY && p != FRT_PRECISION_FAST32)
+        return fail("precision " + std::to_string(P->precision) + " is not supported");
+    if (p == FRT_PRECISION_FAST32 && !shade_split())
+        return fail("precision fast32 is not supported with FRT_SHADE_SPLIT=0 (the unsplit k_shade is binary64 only)");
+    h->fast32 = p == FRT_PRECISION_FAST32;
+    return 0;
+}
+
+// the lights' points as binary32 offsets from each light's centroid, and the centroids (frt::Light32), from the
+// device's binary64 points: once per handle, by its first fast frame
+static int ensure_light32(frt_scene_handle* h) {
+    if (h->light32.off != nullptr || h->S.num_lights == 0) return 0;
+    int64_t len = 0;
+    for (const frt_light& L : h->host_lights)
+        len = std::max<int64_t>(len, L.points + 3 * (int64_t)L.num_samples * std::max(1, L.rows));
+    if (len == 0 || h->S.light_points == nullptr) return 0;
+    std::vector<double> pts((size_t)len);
+    FRT_HIP(hipMemcpy(pts.data(), h->S.light_points, (size_t)len * sizeof(double), hipMemcpyDeviceToHost));
+    std::vector<float> off((size_t)len + 4, 0.0f);  // (a light without samples still has its first point's words read)
+    std::vector<double> cent((size_t)h->S.num_lights * 3, 0.0);
+    for (size_t l = 0; l < h->host_lights.size(); ++l) {
+        const frt_light& L = h->host_lights[l];
+        const int64_t np = (int64_t)L.num_samples * std::max(1, L.rows);
+        if (np <= 0) continue;
+        const double* p = pts.data() + L.points;
+        double c[3] = {0.0, 0.0, 0.0};
+        for (int64_t q = 0; q < np; ++q)
+            for (int k = 0; k < 3; ++k) c[k] += p[3 * q + k];
+        for (int k = 0; k < 3; ++k) cent[3 * l + (size_t)k] = c[k] /= (double)np;
+        for (int64_t q = 0; q < np; ++q)
+            for (int k = 0; k < 3; ++k) off[(size_t)(L.points + 3 * q + k)] = (float)(p[3 * q + k] - c[k]);
+    }
+    int rc = 0;
+    const float* doff = upload(h, off.data(), off.size(), rc);
+    const double* dcent = upload(h, cent.data(), cent.size(), rc);
+    if (rc) return rc;
+    h->light32.cent = dcent;
+    h->light32.off = doff;
+    return 0;
+}
+
 // a failed frame leaves no half-built state behind: photon maps traced by it (maybe truncated by a
 // store overflow) are not reused by the next frame with the same seed
 static int render_impl(frt_scene_handle* h, const frt_frame_params* P, double* dev_out, frt_frame_stats* st) {
@@ -4740,6 +5075,8 @@ static int render_impl(frt_scene_handle* h, const frt_frame_params* P, double* d
 static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* dev_out, frt_frame_stats* st) {
     using namespace frt;
     FRT_HIP(hipSetDevice(h->device));
+    if (frame_precision(h, P)) return -1;
+    if (h->fast32 && ensure_light32(h)) return -1;
     const int64_t hs = h->S.cam.hsize;
     const int64_t stride = P->row_stride > 0 ? P->row_stride : 1;
     int64_t nrows = 0;
@@ -4978,11 +5315,19 @@ static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* 
                     FRT_HIP(hipStreamSynchronize(h->stream));
                     for (int sgi = 0; sgi < kShadeSegs; ++sgi) st->lit_nodes += lc[(size_t)sgi * jit::kMixLine];
                 }
-                if (split) {
-                    KTimer tl(h, st, 15);  // (inside the shade slot: k_shade_lit alone, sub_ms[7])
 #ifndef FRT_SHADE_LIT_BLOCK
 #define FRT_SHADE_LIT_BLOCK 64  // (one wave per block: 9.15 -> 8.83 ms per headline frame, profiles/r05_ab_shade_block.txt; <= kBlock)
 #endif
+                if (split && h->fast32) {
+                    KTimer tl(h, st, 17);  // (inside the shade slot: k_shade_lit32 alone, sub_ms[9])
+                    hipLaunchKernelGGL(sorted ? k_shade_lit32<true> : k_shade_lit32<false>,
+                                       dim3(grid_for(n, FRT_SHADE_LIT_BLOCK)), dim3(FRT_SHADE_LIT_BLOCK), 0, h->stream,
+                                       h->S, B, L.rec, L.counts, L.surface, h->shade_lit, h->shade_lcount, segcap,
+                                       sorted ? (const uint32_t*)h->lit_flat : nullptr,
+                                       staged ? (const frt::LitStage*)h->lit_stage : nullptr,
+                                       sorted_out ? L.spos : nullptr, h->light32);
+                } else if (split) {
+                    KTimer tl(h, st, 15);  // (inside the shade slot: k_shade_lit alone, sub_ms[7])
                     hipLaunchKernelGGL(sorted ? k_shade_lit<true> : k_shade_lit<false>, dim3(grid_for(n, FRT_SHADE_LIT_BLOCK)),
                                        dim3(FRT_SHADE_LIT_BLOCK), 0,
                                        h->stream, h->S, B, L.rec, L.counts, L.surface, h->shade_lit, h->shade_lcount, segcap,

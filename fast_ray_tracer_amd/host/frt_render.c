@@ -16,6 +16,9 @@
  *   FRT_GPUS=<n>           devices 0..n-1;  FRT_DEVICE=<n>: that one device
  *   FRT_SEED=<u64>         counter-RNG seed for multi-row area-light caches
  *   FRT_STATS_OUT=<file>   write a JSON line of frame statistics
+ *   FRT_PRECISION=fast32|parity   the frame's shading precision (the engine reads it at every frame; default
+ *                          parity; include/frt_device.h enum frt_precision). As an FRT_* variable it is part of
+ *                          knob_signature, so a change of mode does not reuse the kept handles
  *
  * The frt_capture_* functions let a harness compile an unmodified generated
  * main.c with -Drender_multi=frt_capture_render_multi to obtain the built

@@ -26,7 +26,11 @@ _host = None
 class FrameParams(ctypes.Structure):
     _fields_ = [("row_begin", ctypes.c_int64), ("row_end", ctypes.c_int64), ("row_stride", ctypes.c_int64),
                 ("seed", ctypes.c_uint64), ("batch_samples", ctypes.c_int64),
-                ("count_reference_rays", ctypes.c_int32), ("pad", ctypes.c_int32)]
+                ("count_reference_rays", ctypes.c_int32), ("precision", ctypes.c_int32)]
+
+
+# frt_frame_params.precision (include/frt_device.h enum frt_precision); None: the environment decides, else parity
+PRECISION = {None: 0, "parity": 1, "fast32": 2}
 
 
 class FrameStats(ctypes.Structure):
@@ -47,7 +51,7 @@ class FrameStats(ctypes.Structure):
     def as_dict(self) -> dict:
         names = ["trace", "shadow", "shade", "combine", "resolve", "trace_primary", "prepare", "gi"]
         subs = ["frt_jit_beam", "frt_jit_shadow", "k_gather_est", "k_gather_hit", "frt_jit_tile", "frt_jit_sub",
-                "frt_jit_subtile", "k_shade_lit", "k_lit_sort"]
+                "frt_jit_subtile", "k_shade_lit", "k_lit_sort", "k_shade_lit32"]
         return {
             "primary_rays": int(self.primary_rays), "secondary_rays": int(self.secondary_rays),
             "shadow_rays": int(self.shadow_rays), "pruned_secondary": int(self.pruned_secondary),
@@ -108,6 +112,10 @@ def host_lib(auto_build: bool = False) -> ctypes.CDLL:
         if lib.frt_frame_stats_size() != ctypes.sizeof(FrameStats):  # (a stale library against this mirror)
             raise RuntimeError("frt: frt_frame_stats is %d bytes in %s, runtime.py FrameStats %d: rebuild"
                                % (lib.frt_frame_stats_size(), build.DEVICE_LIB, ctypes.sizeof(FrameStats)))
+        lib.frt_frame_params_size.restype = ctypes.c_size_t
+        if lib.frt_frame_params_size() != ctypes.sizeof(FrameParams):
+            raise RuntimeError("frt: frt_frame_params is %d bytes in %s, runtime.py FrameParams %d: rebuild"
+                               % (lib.frt_frame_params_size(), build.DEVICE_LIB, ctypes.sizeof(FrameParams)))
         _host = lib
         return lib
 
@@ -173,8 +181,12 @@ class GpuRenderer:
         except Exception:
             pass
 
-    def _params(self, row_begin, row_end, row_stride, seed, batch_samples):
+    def _params(self, row_begin, row_end, row_stride, seed, batch_samples, precision=None):
         p = FrameParams()
+        # (a name from PRECISION; an integer goes to the engine as it is, which refuses the ones it does not know)
+        if not isinstance(precision, int) and precision not in PRECISION:
+            raise ValueError("frt: precision %r is not supported (\"parity\", \"fast32\" or None)" % (precision,))
+        p.precision = precision if isinstance(precision, int) else PRECISION[precision]
         p.row_begin = row_begin
         p.row_end = self.scene.height if row_end is None else row_end
         p.row_stride = row_stride
@@ -187,9 +199,10 @@ class GpuRenderer:
         return len(range(row_begin, row_end, row_stride))
 
     def render(self, row_begin: int = 0, row_end: int | None = None, row_stride: int = 1, seed: int = 0x5EED,
-               batch_samples: int = 0, stats: bool = False):
-        """Render rows into a host array (rows, width, 4) float64."""
-        p = self._params(row_begin, row_end, row_stride, seed, batch_samples)
+               batch_samples: int = 0, stats: bool = False, precision: str | None = None):
+        """Render rows into a host array (rows, width, 4) float64. precision: "parity" (binary64 throughout, the
+        default), "fast32" (the light-point loop in binary32) or None (FRT_PRECISION decides, else parity)."""
+        p = self._params(row_begin, row_end, row_stride, seed, batch_samples, precision)
         n = self.rows_in(p.row_begin, p.row_end, row_stride)
         out = np.zeros((n, self.scene.width, 4), dtype=np.float64)
         st = FrameStats()
@@ -200,9 +213,9 @@ class GpuRenderer:
         return (out, st) if stats else out
 
     def render_into(self, device_ptr: int, row_begin: int = 0, row_end: int | None = None, row_stride: int = 1,
-                    seed: int = 0x5EED, batch_samples: int = 0, stats: bool = False):
-        """Render rows into device memory (e.g. a torch.cuda tensor's data_ptr())."""
-        p = self._params(row_begin, row_end, row_stride, seed, batch_samples)
+                    seed: int = 0x5EED, batch_samples: int = 0, stats: bool = False, precision: str | None = None):
+        """Render rows into device memory (e.g. a torch.cuda tensor's data_ptr()); precision as in render."""
+        p = self._params(row_begin, row_end, row_stride, seed, batch_samples, precision)
         st = FrameStats()
         rc = self.lib.frt_render_rows_device(self.handle, ctypes.byref(p), ctypes.c_void_p(device_ptr),
                                              ctypes.byref(st) if stats else None)
@@ -382,3 +395,10 @@ def encode_ppm(rgba: np.ndarray, use_scaling: bool = True) -> bytes:
     lib.frt_encode_ppm(buf.ctypes.data_as(ctypes.c_void_p), w, h, int(use_scaling),
                        out.ctypes.data_as(ctypes.c_void_p), n)
     return out.tobytes()
+
+
+def ppm_values(rgba: np.ndarray, use_scaling: bool = True) -> np.ndarray:
+    """The (h, w, 3) 16-bit channel values encode_ppm writes (big-endian after the header, one newline at the end)."""
+    h, w = rgba.shape[:2]
+    data = encode_ppm(rgba, use_scaling)
+    return np.frombuffer(data[len(data) - 1 - 6 * h * w:len(data) - 1], dtype=">u2").reshape(h, w, 3).astype(np.int64)

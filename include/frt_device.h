@@ -197,8 +197,20 @@ typedef struct frt_frame_params {
     uint64_t seed;              /* counter-RNG seed for stochastic rows (area-light cache rows, jitter) */
     int64_t batch_samples;      /* camera samples per wavefront batch (0 = engine default) */
     int32_t count_reference_rays; /* 1: also count the rays the reference would cast (slower) */
-    int32_t pad;
+    int32_t precision;          /* enum frt_precision (the former padding word: 0 in every older caller) */
 } frt_frame_params;
+
+/*
+ * Shading precision of a frame. Parity (the default) computes everything in binary64 and matches the reference.
+ * Fast32 computes lighting_microfacet's light-point loop (reference renderer.c:895-979) in binary32 (k_shade_lit32,
+ * fast_ray_tracer_amd/csrc/frt_shade32.hpp); geometry, visibility, recursion and every per-node term stay binary64,
+ * so a fast frame differs from a parity frame only in the value of lit nodes' diffuse and specular sums
+ * (DESIGN.md "Fast shading mode": the error model and the measured mismatch). FRT_PRECISION_DEFAULT leaves the
+ * choice to the environment, read at every frame: FRT_PRECISION=fast32 | parity, else parity. A non-zero value
+ * here wins over the environment. Any other value, or a fast frame with FRT_SHADE_SPLIT=0, makes frt_render_rows*
+ * fail ("precision N is not supported"); nothing falls back silently.
+ */
+enum frt_precision { FRT_PRECISION_DEFAULT = 0, FRT_PRECISION_PARITY = 1, FRT_PRECISION_FAST32 = 2 };
 
 typedef struct frt_frame_stats {
     uint64_t primary_rays;
@@ -219,8 +231,9 @@ typedef struct frt_frame_stats {
     /* kernels inside the slots above (HIP events around each launch on the engine stream):
        0 frt_jit_beam / frt_jit_beam_list (node pair kernel), 1 frt_jit_shadow (per-ray kernel), 2 k_gather_est,
        3 k_gather_hit, 4 frt_jit_tile (tile pair kernel), 5 frt_jit_sub (sub-part pair kernel), 6 frt_jit_subtile
-       (sub-tile pair kernel), 7 k_shade_lit (the shading of the path nodes some light reaches), 8 k_lit_scan +
-       k_lit_scatter (the lit list in light-row order, multi-row lights); 9-15 unused */
+       (sub-tile pair kernel), 7 k_shade_lit (the shading of the path nodes some light reaches; 0 in a fast32 frame), 8 k_lit_scan +
+       k_lit_scatter (the lit list in light-row order, multi-row lights), 9 k_shade_lit32 (k_shade_lit's place in a
+       fast32 frame; 0 in a parity frame); 10-15 unused */
     double sub_ms[16];
     uint64_t sub_launches[16];
     uint64_t shadow_rays_walked;  /* shadow rays walked one by one; the rest of shadow_rays were resolved
@@ -256,6 +269,9 @@ void frt_host_pinned_free(void *p);
  * checks its size against it before passing one in (no device needed) */
 size_t frt_frame_stats_size(void);
 
+/* sizeof(frt_frame_params) as this library was built, for the same check (runtime.py FrameParams) */
+size_t frt_frame_params_size(void);
+
 /* message of the last failing call on this thread */
 const char *frt_last_error(void);
 
@@ -290,6 +306,16 @@ int frt_mesh_check(const frt_scene *scene, int64_t *out, int n);
  * estimates against their 2^-46 relative bound, on n lanes of random vectors; returns the number of
  * failed checks (0: all hold), or -1 on a HIP error. */
 int64_t frt_math_selftest(int64_t n, uint64_t seed);
+
+/* Diagnostics (current device): the fast mode's binary32 light-point term against the binary64 term on n lanes of
+ * random inputs: unit normal and eye, |over_point|, |light point| <= 8 with |diff| >= 1, Ns from {0, 1, 2.5, 10, 200,
+ * 1000, 5000}, a share of lanes with n.l and n.e down to 1e-30 and with n.l slightly negative. Returns the number
+ * of lanes whose binary32 result is not finite while the binary64 one is, plus the lanes whose diffuse term l.n is
+ * off by more than 32 * 2^-24 (the bound of those input ranges: frt_shade32.hpp), or -1 on a HIP error. For the
+ * record, not gated: out[0] the worst deviation of the specular factor relative to its binary64 value over the
+ * lanes with l.n >= 2^-16, out[1] the same over their lanes with Ns <= 200, out[2] the worst absolute deviation of
+ * l.n, out[3] the number of lanes behind out[0] (min(nout, 4) written; out may be NULL). */
+int64_t frt_shade32_selftest(int64_t n, uint64_t seed, double *out, int nout);
 
 /* Counters of the scene-specialised kernels' code-object cache since the library was loaded (no device
  * needed): out[0] hiprtc compiles, out[1] code objects read from the on-disk cache, out[2] code objects
