@@ -5,8 +5,9 @@
  * (double[4]) canvas, row 0 at the top, written as a 16-bit big-endian P6 PPM
  * with the reference's normalisation (reference src/libs/canvas/canvas.c:150-327)
  * and as a 16-bit sRGB PNG through libpng (canvas.c:376-510). Texture readers
- * (PNG, ASCII PPM) follow canvas.c:330-672. The encode runs on the host after
- * the device canvas has been copied back.
+ * (PNG, ASCII PPM) follow canvas.c:330-672. The 16-bit values come from the host
+ * pass below or, byte-identical, from the device (FRT_ENCODE, frt_encode.hip); the
+ * file and libpng writing stay here.
  */
 #include <math.h>
 #include <pthread.h>
@@ -14,6 +15,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <time.h>
 
 #include <png.h>
 
@@ -198,33 +200,59 @@ quantize(double srgb, double srgb_max, double inverse)
     return (uint16_t)floor(srgb * inverse);
 }
 
-Ppm
-construct_ppm(Canvas c, bool use_scaling)
+/*
+ * One pixel's three 16-bit values: the scaling / clamp statements, rgb_to_srgb and quantize of the reference's
+ * construct_ppm (canvas.c:150-327) and write_png (canvas.c:376-510). The only definition of that arithmetic: the
+ * host pass calls it for every pixel, the device path (frt_encode.hip) for the values it left undecided.
+ */
+static void
+encode_pixel(const Color px, int mode, const double srgb_max[3], const double inv[3], uint16_t q[3])
 {
-    char header[32];
-    int n = snprintf(header, sizeof(header), "P6\n%zu %zu\n65535\n", c->width, c->height);
-    size_t npx = c->width * c->height;
-    Ppm ppm = ppm_alloc(npx * 6 + (size_t)n + 1);
-    unsigned char *out = ppm->arr;
-    memcpy(out, header, (size_t)n);
-    out += n;
-
-    /* pass 1: per-channel linear maximum (starts at 0) */
-    Color rgb_max = {0.0, 0.0, 0.0, 0.0};
-    for (size_t i = 0; i < npx; ++i) {
+    Color t, s;
+    memcpy(t, px, sizeof(Color));
+    if (mode == FRT_ENCODE_PPM_SCALED) {
+        double len = t[0] + t[1] + t[2];
+        if (len > FRT_SQRT3) {
+            color_scale(t, 1.0 / len);
+            color_scale(t, FRT_SQRT3);
+        }
+    } else {
         for (int k = 0; k < 3; ++k) {
-            if (c->arr[i][k] > rgb_max[k]) {
-                rgb_max[k] = c->arr[i][k];
+            if (t[k] > 1.0) {
+                t[k] = 1.0;
+            } else if (t[k] < 0) {
+                t[k] = 0.0;
             }
         }
     }
-    print_color(rgb_max);
+    rgb_to_srgb(t, s);
+    for (int k = 0; k < 3; ++k) {
+        q[k] = quantize(s[k], srgb_max[k], inv[k]);
+    }
+}
 
-    /* pass 2: maximum of sRGB(pixel / rgb_max) */
-    Color srgb_max = {0.0, 0.0, 0.0, 0.0};
+/* pass 1: per-channel linear maximum (starts at 0) */
+static void
+host_rgb_max(const Color *arr, size_t npx, Color rgb_max)
+{
+    memset(rgb_max, 0, sizeof(Color));
+    for (size_t i = 0; i < npx; ++i) {
+        for (int k = 0; k < 3; ++k) {
+            if (arr[i][k] > rgb_max[k]) {
+                rgb_max[k] = arr[i][k];
+            }
+        }
+    }
+}
+
+/* pass 2: maximum of sRGB(pixel / rgb_max) */
+static void
+host_srgb_max(const Color *arr, size_t npx, const Color rgb_max, Color srgb_max)
+{
+    memset(srgb_max, 0, sizeof(Color));
     for (size_t i = 0; i < npx; ++i) {
         Color t, s;
-        memcpy(t, c->arr[i], sizeof(Color));
+        memcpy(t, arr[i], sizeof(Color));
         t[0] /= rgb_max[0];
         t[1] /= rgb_max[1];
         t[2] /= rgb_max[2];
@@ -235,37 +263,251 @@ construct_ppm(Canvas c, bool use_scaling)
             }
         }
     }
-    print_color(srgb_max);
+}
 
-    double inv[3] = {65535.0 / srgb_max[0], 65535.0 / srgb_max[1], 65535.0 / srgb_max[2]};
+/* construct_ppm's srgb_max by its two full passes (the device path takes rgb_to_srgb(1.0) instead: DESIGN.md
+ * "Image encode"; tests/test_encode.py compares the two) */
+void
+frt_srgb_max_full(const double *rgba, size_t width, size_t height, double out[3])
+{
+    Color rgb_max, srgb_max;
+    host_rgb_max((const Color *)rgba, width * height, rgb_max);
+    host_srgb_max((const Color *)rgba, width * height, rgb_max, srgb_max);
+    memcpy(out, srgb_max, 3 * sizeof(double));
+}
 
+static double
+clock_ms(void)
+{
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (double)ts.tv_sec * 1e3 + (double)ts.tv_nsec * 1e-6;
+}
+
+/* the first device render_multi / frt_host_prepare last used in this process, -1 while none was: FRT_ENCODE=auto
+ * takes the device only then (a process that only writes an image does not pay HIP's start-up for it) */
+static int g_encode_device = -1;
+
+void
+frt_encode_note_device(int device)
+{
+    __atomic_store_n(&g_encode_device, device, __ATOMIC_RELAXED);
+}
+
+static _Thread_local frt_encode_stats t_encode_last;
+
+void
+frt_encode_last(frt_encode_stats *out)
+{
+    *out = t_encode_last;
+}
+
+size_t
+frt_encode_stats_size(void)
+{
+    return sizeof(frt_encode_stats);
+}
+
+static const char *const decline_names[] = {"taken", "a channel's maximum is 0", "a non-finite pixel",
+                                            "too many undecided values", "no usable device", "image too large"};
+
+/* FRT_ENCODE=host | device | auto (default auto), read at every call */
+static int
+encode_backend_env(void)
+{
+    const char *e = getenv("FRT_ENCODE");
+    if (e != NULL && strcmp(e, "host") == 0) {
+        return FRT_ENCODE_HOST;
+    }
+    if (e != NULL && strcmp(e, "device") == 0) {
+        return FRT_ENCODE_DEVICE;
+    }
+    return FRT_ENCODE_AUTO;
+}
+
+/* the reason the device would decline this canvas for, had there been one (the host pass reports it) */
+static int
+classify_canvas(const Color *arr, size_t npx, int mode, const Color rgb_max)
+{
     for (size_t i = 0; i < npx; ++i) {
-        Color t, s;
-        memcpy(t, c->arr[i], sizeof(Color));
-        if (use_scaling) {
-            double len = t[0] + t[1] + t[2];
-            if (len > FRT_SQRT3) {
-                color_scale(t, 1.0 / len);
-                color_scale(t, FRT_SQRT3);
-            }
-        } else {
-            for (int k = 0; k < 3; ++k) {
-                if (t[k] > 1.0) {
-                    t[k] = 1.0;
-                } else if (t[k] < 0) {
-                    t[k] = 0.0;
-                }
-            }
-        }
-        rgb_to_srgb(t, s);
         for (int k = 0; k < 3; ++k) {
-            uint16_t q = quantize(s[k], srgb_max[k], inv[k]);
-            *out++ = (unsigned char)(q >> 8);
-            *out++ = (unsigned char)(q & 0xFF);
+            if (!isfinite(arr[i][k])) {
+                return FRT_ENCODE_NON_FINITE;
+            }
         }
     }
-    *out = '\n';
+    if (mode != FRT_ENCODE_PNG && (rgb_max[0] == 0.0 || rgb_max[1] == 0.0 || rgb_max[2] == 0.0)) {
+        return FRT_ENCODE_ZERO_MAX;
+    }
+    return FRT_ENCODE_NO_DEVICE;
+}
+
+static void
+put16(unsigned char *out, const uint16_t q)
+{
+    out[0] = (unsigned char)(q >> 8);
+    out[1] = (unsigned char)(q & 0xFF);
+}
+
+/*
+ * The 6 * width * height payload bytes of a canvas in host memory (arr) or device memory (dev_rgba, arr NULL).
+ * print: construct_ppm's two print_color lines. Returns 0, or -1 when a device-resident canvas could not be
+ * fetched for the host pass.
+ */
+static int
+encode16(const Color *arr, const double *dev_rgba, size_t width, size_t height, int mode, int backend, int device,
+         int print, unsigned char *out, frt_encode_stats *st)
+{
+    const size_t npx = width * height;
+    const int hint = __atomic_load_n(&g_encode_device, __ATOMIC_RELAXED);
+    memset(st, 0, sizeof(*st));
+    st->values = 3 * (uint64_t)npx;
+    st->mode = mode;
+    st->device = -1;
+    if (backend == FRT_ENCODE_AUTO) {
+        backend = hint >= 0 ? FRT_ENCODE_DEVICE : FRT_ENCODE_HOST;
+    }
+    if (device < 0) {
+        device = hint >= 0 ? hint : 0;
+    }
+    if (backend == FRT_ENCODE_DEVICE && npx > 0) {
+        /* the quantiser's constants by the host's own arithmetic: with every rgb_max > 0 the pixel holding a
+         * maximum gives x / x = 1.0 and no other quotient exceeds 1, so srgb_max is rgb_to_srgb(1.0) */
+        const Color one = {1.0, 1.0, 1.0, 0.0};
+        Color s_one;
+        double srgb_max[4] = {1.0, 1.0, 1.0, 0.0}, inv[3] = {65535.0, 65535.0, 65535.0};
+        unsigned short code_one[3];
+        rgb_to_srgb(one, s_one);
+        for (int k = 0; k < 3; ++k) {
+            if (mode != FRT_ENCODE_PNG) {
+                srgb_max[k] = s_one[k];
+                inv[k] = 65535.0 / srgb_max[k];
+            }
+            code_one[k] = quantize(s_one[k], srgb_max[k], inv[k]);
+        }
+        const size_t cap = (size_t)(st->values / 64) + 1;
+        uint32_t *und_idx = (uint32_t *)malloc(cap * sizeof(uint32_t));
+        double *und_px = arr == NULL ? (double *)malloc(cap * sizeof(Color)) : NULL;
+        int rc = -1;
+        if (und_idx != NULL && (arr != NULL || und_px != NULL)) {
+            rc = frt_encode16_device(arr != NULL ? (const double *)arr : dev_rgba, arr == NULL, width, height, mode,
+                                     device, srgb_max, inv, code_one, out, und_idx, und_px, st);
+        } else {
+            st->decline = FRT_ENCODE_NO_DEVICE;
+        }
+        if (rc == 0) {
+            const double p0 = clock_ms();
+            for (uint64_t j = 0; j < st->undecided; ++j) {
+                const size_t p = und_idx[j] / 3;
+                const int k = (int)(und_idx[j] % 3);
+                uint16_t q[3];
+                encode_pixel(arr != NULL ? arr[p] : (const double *)(und_px + 4 * j), mode, srgb_max, inv, q);
+                put16(out + 6 * p + 2 * k, q[k]);
+            }
+            st->patch_ms = clock_ms() - p0;
+            if (print) {
+                Color m = {st->rgb_max[0], st->rgb_max[1], st->rgb_max[2], 0.0};
+                print_color(m);
+                print_color(srgb_max);
+            }
+        }
+        free(und_idx);
+        free(und_px);
+        if (rc == 0) {
+            return 0;
+        }
+        fprintf(stderr, "frt: image encode falls back to the host pass: %s%s%s\n", decline_names[st->decline],
+                rc < 0 ? ": " : "", rc < 0 ? frt_encode_error() : "");
+    }
+
+    /* the host pass: the reference's three passes */
+    const int wanted_device = backend == FRT_ENCODE_DEVICE;
+    const int decline = st->decline;
+    Color *fetched = NULL;
+    if (arr == NULL) {
+        fetched = (Color *)malloc(npx * sizeof(Color));
+        if (fetched == NULL || frt_encode_fetch(fetched, dev_rgba, npx * sizeof(Color), device) != 0) {
+            free(fetched);
+            return -1;
+        }
+        arr = fetched;
+    }
+    const double h0 = clock_ms();
+    Color rgb_max = {0.0, 0.0, 0.0, 0.0}, srgb_max = {1.0, 1.0, 1.0, 0.0};
+    double inv[3] = {65535.0, 65535.0, 65535.0};
+    if (mode != FRT_ENCODE_PNG) {
+        host_rgb_max(arr, npx, rgb_max);
+        if (print) {
+            print_color(rgb_max);
+        }
+        host_srgb_max(arr, npx, rgb_max, srgb_max);
+        if (print) {
+            print_color(srgb_max);
+        }
+        for (int k = 0; k < 3; ++k) {
+            inv[k] = 65535.0 / srgb_max[k];
+        }
+    }
+    for (size_t i = 0; i < npx; ++i) {
+        uint16_t q[3];
+        encode_pixel(arr[i], mode, srgb_max, inv, q);
+        for (int k = 0; k < 3; ++k) {
+            put16(out, q[k]);
+            out += 2;
+        }
+    }
+    const double host_ms = clock_ms() - h0;
+    st->backend = FRT_ENCODE_HOST;
+    st->undecided = 0;
+    st->host_ms = host_ms;
+    memcpy(st->rgb_max, rgb_max, 3 * sizeof(double));
+    memcpy(st->srgb_max, srgb_max, 3 * sizeof(double));
+    st->decline = !wanted_device ? FRT_ENCODE_TAKEN
+                  : decline == FRT_ENCODE_NO_DEVICE ? classify_canvas(arr, npx, mode, rgb_max) : decline;
+    free(fetched);
+    return 0;
+}
+
+int
+frt_encode16(const double *rgba, int rgba_on_device, size_t width, size_t height, int mode, int backend, int device,
+             unsigned char *out, frt_encode_stats *st)
+{
+    frt_encode_stats local;
+    if (mode < FRT_ENCODE_PPM_SCALED || mode > FRT_ENCODE_PNG || backend < FRT_ENCODE_HOST ||
+        backend > FRT_ENCODE_AUTO) {
+        return -1;
+    }
+    int rc = encode16(rgba_on_device ? NULL : (const Color *)rgba, rgba, width, height, mode, backend, device, 0, out,
+                      &local);
+    t_encode_last = local;
+    if (st != NULL) {
+        *st = local;
+    }
+    return rc;
+}
+
+static Ppm
+construct_ppm_with(Canvas c, bool use_scaling, int backend)
+{
+    char header[32];
+    int n = snprintf(header, sizeof(header), "P6\n%zu %zu\n65535\n", c->width, c->height);
+    size_t npx = c->width * c->height;
+    Ppm ppm = ppm_alloc(npx * 6 + (size_t)n + 1);
+    unsigned char *out = ppm->arr;
+    memcpy(out, header, (size_t)n);
+    out += n;
+    frt_encode_stats st;
+    encode16(c->arr, NULL, c->width, c->height, use_scaling ? FRT_ENCODE_PPM_SCALED : FRT_ENCODE_PPM_CLAMPED, backend,
+             -1, 1, out, &st);
+    t_encode_last = st;
+    out[npx * 6] = '\n';
     return ppm;
+}
+
+Ppm
+construct_ppm(Canvas c, bool use_scaling)
+{
+    return construct_ppm_with(c, use_scaling, encode_backend_env());
 }
 
 static char *
@@ -341,23 +583,11 @@ write_png(Canvas c, const char *file_name)
 
     size_t npx = c->width * c->height;
     buffer = (uint16_t *)malloc(npx * 3 * sizeof(uint16_t));
-    unsigned char *out = (unsigned char *)buffer;
-    for (size_t i = 0; i < npx; ++i) {
-        Color t, s;
-        memcpy(t, c->arr[i], sizeof(Color));
-        for (int k = 0; k < 3; ++k) {
-            if (t[k] > 1.0) {
-                t[k] = 1.0;
-            } else if (t[k] < 0) {
-                t[k] = 0.0;
-            }
-        }
-        rgb_to_srgb(t, s);
-        for (int k = 0; k < 3; ++k) {
-            uint16_t q = quantize(s[k], 1.0, 65535.0);
-            *out++ = (unsigned char)(q >> 8);
-            *out++ = (unsigned char)(q & 0xFF);
-        }
+    {
+        frt_encode_stats st;
+        encode16(c->arr, NULL, c->width, c->height, FRT_ENCODE_PNG, encode_backend_env(), -1, 0,
+                 (unsigned char *)buffer, &st);
+        t_encode_last = st;
     }
     for (size_t row = 0; row < c->height; ++row) {
         png_write_row(png, (png_bytep)buffer + 3 * sizeof(uint16_t) * row * c->width);
@@ -489,7 +719,7 @@ frt_encode_ppm(const double *rgba, size_t width, size_t height, int use_scaling,
     c.height = height;
     c.super_sample = false;
     c.color_space_fn = NULL;
-    Ppm p = construct_ppm(&c, use_scaling != 0);
+    Ppm p = construct_ppm_with(&c, use_scaling != 0, FRT_ENCODE_HOST);
     size_t n = p->len;
     if (out != NULL && cap >= n) {
         memcpy(out, p->arr, n);

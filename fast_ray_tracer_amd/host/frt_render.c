@@ -100,6 +100,7 @@ frt_host_prepare(Camera cam, World w, size_t usteps, size_t vsteps, bool jitter,
         snprintf(g_host_error, sizeof(g_host_error), "%s", frt_last_error());
         return NULL;
     }
+    frt_encode_note_device(device);
     return h;
 }
 
@@ -281,7 +282,7 @@ static char *
 knob_signature(void)
 {
     static const char *const per_call[] = {"FRT_DEVICES=", "FRT_GPUS=", "FRT_DEVICE=", "FRT_SEED=", "FRT_STATS_OUT=",
-                                           "FRT_RM_KEEP="};
+                                           "FRT_RM_KEEP=", "FRT_ENCODE="};
     size_t n = 0, len = 1;
     for (char **e = environ; e != NULL && *e != NULL; ++e) {
         n += strncmp(*e, "FRT_", 4) == 0;
@@ -577,6 +578,7 @@ render_multi_locked(Camera cam, World w, size_t usteps, size_t vsteps, bool jitt
             }
         }
         g_rm_phases[11] = now_ms() - place0;
+        frt_encode_note_device(dev[0]);  /* (write_ppm_file / write_png: FRT_ENCODE=auto encodes there) */
         if (stats_path) {
             write_stats(stats_path, &total, cam, usteps, vsteps, n);
         }

@@ -35,6 +35,11 @@ void ppm_free(Ppm p);
 Canvas frt_canvas_alloc_pinned(size_t width, size_t height, bool super_sample, void (*color_space_fn)(const Color, Color));
 void frt_canvas_pool_release(void);
 
+/* (frt: the 16-bit values of write_ppm_file / write_png come from the host pass or, byte-identical, from the device:
+ * FRT_ENCODE=host | device | auto, default auto = the device once this process has rendered on one.
+ * frt_encode_note_device records that device (render_multi, frt_host_prepare)) */
+void frt_encode_note_device(int device);
+
 void canvas_write_pixels(Canvas c, int col, int row, Color *colors, size_t num);
 void canvas_write_pixel(Canvas c, int col, int row, Color color);
 void canvas_pixel_at(Canvas c, int col, int row, Color res);

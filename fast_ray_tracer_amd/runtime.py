@@ -73,6 +73,29 @@ class FrameStats(ctypes.Structure):
         }
 
 
+class EncodeStats(ctypes.Structure):
+    """frt_encode_stats (include/frt_device.h)."""
+    _fields_ = [("values", ctypes.c_uint64), ("undecided", ctypes.c_uint64), ("backend", ctypes.c_int32),
+                ("decline", ctypes.c_int32), ("mode", ctypes.c_int32), ("device", ctypes.c_int32),
+                ("rgb_max", ctypes.c_double * 3), ("srgb_max", ctypes.c_double * 3), ("upload_ms", ctypes.c_double),
+                ("kernel_ms", ctypes.c_double), ("readback_ms", ctypes.c_double), ("patch_ms", ctypes.c_double),
+                ("host_ms", ctypes.c_double)]
+
+    def as_dict(self) -> dict:
+        return {"values": int(self.values), "undecided": int(self.undecided),
+                "backend": ENCODE_BACKENDS[self.backend], "decline": ENCODE_DECLINES[self.decline],
+                "mode": ENCODE_MODES[self.mode], "device": int(self.device), "rgb_max": list(self.rgb_max),
+                "srgb_max": list(self.srgb_max), "upload_ms": float(self.upload_ms),
+                "kernel_ms": float(self.kernel_ms), "readback_ms": float(self.readback_ms),
+                "patch_ms": float(self.patch_ms), "host_ms": float(self.host_ms)}
+
+
+# enum frt_encode_mode / frt_encode_backend / frt_encode_decline (include/frt_device.h), by value
+ENCODE_MODES = ("ppm_scaled", "ppm_clamped", "png")
+ENCODE_BACKENDS = ("host", "device", "auto")
+ENCODE_DECLINES = (None, "zero_max", "non_finite", "over_cap", "no_device", "too_large")
+
+
 def host_lib(auto_build: bool = False) -> ctypes.CDLL:
     """Load libfrt_host.so (which pulls in libfrt_device.so) with global symbols."""
     global _host
@@ -108,6 +131,24 @@ def host_lib(auto_build: bool = False) -> ctypes.CDLL:
         lib.frt_scene_release.argtypes = [vp]
         lib.frt_encode_ppm.restype = ctypes.c_size_t
         lib.frt_encode_ppm.argtypes = [vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_size_t]
+        lib.frt_encode16.restype = ctypes.c_int
+        lib.frt_encode16.argtypes = [vp, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
+                                     ctypes.c_int, vp, ctypes.POINTER(EncodeStats)]
+        lib.frt_encode_last.restype = None
+        lib.frt_encode_last.argtypes = [ctypes.POINTER(EncodeStats)]
+        lib.frt_encode_stats_size.restype = ctypes.c_size_t
+        if lib.frt_encode_stats_size() != ctypes.sizeof(EncodeStats):
+            raise RuntimeError("frt: frt_encode_stats is %d bytes in %s, runtime.py EncodeStats %d: rebuild"
+                               % (lib.frt_encode_stats_size(), build.HOST_LIB, ctypes.sizeof(EncodeStats)))
+        lib.frt_srgb_max_full.restype = None
+        lib.frt_srgb_max_full.argtypes = [vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(ctypes.c_double)]
+        lib.frt_encode_selftest.restype = ctypes.c_int64
+        lib.frt_encode_selftest.argtypes = [ctypes.c_int64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_double),
+                                            ctypes.c_int]
+        lib.write_ppm_file.restype = ctypes.c_int
+        lib.write_ppm_file.argtypes = [vp, ctypes.c_bool, ctypes.c_char_p]
+        lib.write_png.restype = ctypes.c_int
+        lib.write_png.argtypes = [vp, ctypes.c_char_p]
         lib.frt_frame_stats_size.restype = ctypes.c_size_t
         if lib.frt_frame_stats_size() != ctypes.sizeof(FrameStats):  # (a stale library against this mirror)
             raise RuntimeError("frt: frt_frame_stats is %d bytes in %s, runtime.py FrameStats %d: rebuild"
@@ -222,6 +263,17 @@ class GpuRenderer:
         if rc != 0:
             raise RuntimeError("frt render failed: " + self.lib.frt_last_error().decode())
         return st if stats else None
+
+
+    def render_encoded(self, mode: str = "ppm_scaled", **render_args):
+        """Render the whole frame into device memory (a torch tensor, frt_render_rows_device) and encode it there
+        (frt_encode16 from device memory: the canvas never crosses to the host). Returns ((h, w, 3) uint16, encode
+        stats dict); render_args as render_into's (seed, batch_samples, precision)."""
+        import torch
+        with torch.cuda.device(self.device):
+            frame = torch.empty((self.scene.height, self.scene.width, 4), dtype=torch.float64, device="cuda")
+        self.render_into(frame.data_ptr(), **render_args)
+        return _encode16(frame.data_ptr(), True, self.scene.width, self.scene.height, mode, "device", self.device)
 
 
 def render_multi(scene: Scene, devices: str | None = None) -> np.ndarray:
@@ -402,3 +454,88 @@ def ppm_values(rgba: np.ndarray, use_scaling: bool = True) -> np.ndarray:
     h, w = rgba.shape[:2]
     data = encode_ppm(rgba, use_scaling)
     return np.frombuffer(data[len(data) - 1 - 6 * h * w:len(data) - 1], dtype=">u2").reshape(h, w, 3).astype(np.int64)
+
+
+def _encode16(ptr: int, on_device: bool, w: int, h: int, mode: str, backend: str, device: int):
+    lib = host_lib()
+    if mode not in ENCODE_MODES or backend not in ENCODE_BACKENDS:
+        raise ValueError("frt: encode mode %r / backend %r is not supported" % (mode, backend))
+    out = np.zeros((h, w, 3), dtype=">u2")
+    st = EncodeStats()
+    rc = lib.frt_encode16(ctypes.c_void_p(ptr), int(on_device), w, h, ENCODE_MODES.index(mode),
+                          ENCODE_BACKENDS.index(backend), device, out.ctypes.data_as(ctypes.c_void_p),
+                          ctypes.byref(st))
+    if rc != 0:
+        raise RuntimeError("frt: encode16 failed (rc %d)" % rc)
+    return out.astype(np.uint16), st.as_dict()
+
+
+def _rgba64(rgba: np.ndarray) -> np.ndarray:
+    h, w = rgba.shape[:2]
+    buf = np.zeros((h, w, 4), dtype=np.float64)
+    buf[:, :, :min(4, rgba.shape[2])] = rgba[:, :, :min(4, rgba.shape[2])]
+    return buf
+
+
+def encode16(rgba: np.ndarray, mode: str = "ppm_scaled", backend: str = "device", device: int = 0):
+    """The 16-bit values write_ppm_file(c, true / false, ..) ("ppm_scaled" / "ppm_clamped") or write_png ("png")
+    write for a (h, w, 3|4) float64 canvas: ((h, w, 3) uint16, stats dict). backend "device": the HIP encode
+    (frt_encode.hip), falling back to the host pass with the reason in stats["decline"]; "host": the host pass;
+    "auto": the device once this process has rendered on one. Either way the values are the host pass's."""
+    _, buf = _canvas_of(rgba)  # (a float64 h x w x 4 array as it is: render_multi's page-locked canvas)
+    return _encode16(buf.ctypes.data, False, buf.shape[1], buf.shape[0], mode, backend, device)
+
+
+def encode_last() -> dict:
+    """What this thread's last encode did (frt_encode_last): write_ppm / write_png / encode16."""
+    st = EncodeStats()
+    host_lib().frt_encode_last(ctypes.byref(st))
+    return st.as_dict()
+
+
+def srgb_max_full(rgba: np.ndarray) -> list:
+    """construct_ppm's srgb_max by its two full host passes (frt_srgb_max_full)."""
+    buf = _rgba64(rgba)
+    out = (ctypes.c_double * 3)()
+    host_lib().frt_srgb_max_full(buf.ctypes.data_as(ctypes.c_void_p), buf.shape[1], buf.shape[0], out)
+    return list(out)
+
+
+def encode_selftest(n: int, seed: int = 1):
+    """frt_encode_selftest on the current device: (failed lanes, [worst sRGB deviation, worst pow deviation,
+    lanes whose sRGB value differs from the host's])."""
+    out = (ctypes.c_double * 3)()
+    bad = host_lib().frt_encode_selftest(n, seed, out, 3)
+    return int(bad), list(out)
+
+
+class _CanvasStruct(ctypes.Structure):  # struct canvas (host/src/libs/canvas/canvas.h)
+    _fields_ = [("arr", ctypes.c_void_p), ("width", ctypes.c_size_t), ("height", ctypes.c_size_t),
+                ("super_sample", ctypes.c_bool), ("color_space_fn", ctypes.c_void_p)]
+
+
+def _canvas_of(rgba: np.ndarray):
+    if rgba.dtype == np.float64 and rgba.ndim == 3 and rgba.shape[2] == 4 and rgba.flags["C_CONTIGUOUS"]:
+        buf = rgba  # (render_multi's page-locked array as it is)
+    else:
+        buf = _rgba64(rgba)
+    return _CanvasStruct(buf.ctypes.data, buf.shape[1], buf.shape[0], False, None), buf
+
+
+def write_ppm(path: str, rgba: np.ndarray, use_scaling: bool = True) -> dict:
+    """write_ppm_file(canvas, use_scaling, path) of the host library (it appends ".ppm"; FRT_ENCODE selects the
+    encode's backend); returns what the encode did."""
+    c, keep = _canvas_of(rgba)
+    if host_lib().write_ppm_file(ctypes.byref(c), bool(use_scaling), os.fsencode(path)) != 0:
+        raise RuntimeError("frt: write_ppm_file failed: " + path)
+    del keep
+    return encode_last()
+
+
+def write_png(path: str, rgba: np.ndarray) -> dict:
+    """write_png(canvas, path) of the host library (it appends ".png"); returns what the encode did."""
+    c, keep = _canvas_of(rgba)
+    if host_lib().write_png(ctypes.byref(c), os.fsencode(path)) != 0:
+        raise RuntimeError("frt: write_png failed: " + path)
+    del keep
+    return encode_last()

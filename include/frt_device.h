@@ -352,6 +352,82 @@ int frt_pm_estimate(int device, const double *pos, const double *power, const ui
                     const double *queries, int64_t nq, double radius, int32_t k, double cone_k,
                     double *irrad, int64_t *found);
 
+/*
+ * Image encode (fast_ray_tracer_amd/csrc/frt_encode.hip): the 16-bit values of write_ppm_file / write_png
+ * (reference src/libs/canvas/canvas.c:150-327, 376-510) computed on the device, byte-identical to the host pass
+ * (DESIGN.md "Image encode"). Everything but pow(t, 1/2.4) is plain IEEE arithmetic the device repeats bit for
+ * bit; a value whose code the device's pow cannot prove (within FRT_ENCODE_MARGIN of a code boundary or of
+ * srgb_max) is left undecided and listed, and the caller (host/frt_canvas.c) recomputes it with the host's own
+ * arithmetic.
+ */
+enum frt_encode_mode {
+    FRT_ENCODE_PPM_SCALED = 0,  /* write_ppm_file(c, true, ..)  */
+    FRT_ENCODE_PPM_CLAMPED = 1, /* write_ppm_file(c, false, ..) */
+    FRT_ENCODE_PNG = 2          /* write_png                    */
+};
+
+enum frt_encode_backend { FRT_ENCODE_HOST = 0, FRT_ENCODE_DEVICE = 1, FRT_ENCODE_AUTO = 2 };
+
+/* why the device did not produce the bytes (the host pass did) */
+enum frt_encode_decline {
+    FRT_ENCODE_TAKEN = 0,        /* the device produced them, or the host backend was asked for */
+    FRT_ENCODE_ZERO_MAX = 1,     /* a channel's maximum is 0 (PPM modes: x / rgb_max is not finite) */
+    FRT_ENCODE_NON_FINITE = 2,   /* a colour channel of some pixel is NaN or infinite */
+    FRT_ENCODE_OVER_CAP = 3,     /* more than 1/64 of the values undecided */
+    FRT_ENCODE_NO_DEVICE = 4,    /* no usable GPU, or a HIP call failed (frt_encode_error) */
+    FRT_ENCODE_TOO_LARGE = 5     /* 3 * width * height does not fit the 32-bit undecided index */
+};
+
+#define FRT_ENCODE_MARGIN 0x1p-40 /* relative distance from a boundary under which a pow-branch value is undecided */
+
+typedef struct frt_encode_stats {
+    uint64_t values;     /* 3 * width * height */
+    uint64_t undecided;  /* values the device left to the host (patched there) */
+    int32_t backend;     /* enum frt_encode_backend: who produced the bytes */
+    int32_t decline;     /* enum frt_encode_decline */
+    int32_t mode;        /* enum frt_encode_mode */
+    int32_t device;      /* the HIP device used, -1 when none */
+    double rgb_max[3];   /* construct_ppm's two printed maxima (PNG: rgb_max as measured, srgb_max 1.0) */
+    double srgb_max[3];
+    double upload_ms;    /* canvas to the device (0 when it was there) */
+    double kernel_ms;    /* the maximum and the quantise kernel (HIP events) */
+    double readback_ms;  /* the bytes, the undecided list and its pixels to the host */
+    double patch_ms;     /* host: recomputing the undecided values */
+    double host_ms;      /* the host pass, when it produced the bytes */
+} frt_encode_stats;
+
+/*
+ * Encode a width x height x 4 binary64 canvas (in host memory, or with rgba_on_device != 0 in device memory on
+ * `device`) into out: 6 * width * height bytes, big-endian 16-bit R G B in pixel order. srgb_max / inverse are the
+ * quantiser's per-channel constants and code_one the code of an input that is exactly 1.0, all three computed by
+ * the caller with the host's arithmetic. The undecided values come back as und_idx[j] = 3 * pixel + channel with
+ * (rgba_on_device only) the pixel's four doubles in und_px[4 * j]; both hold values / 64 entries. Returns 0 when
+ * the bytes are in out (st->backend FRT_ENCODE_DEVICE, st->undecided entries to patch), 1 when the device
+ * declined (st->decline says why; out is unspecified), -1 on a HIP error (frt_encode_error; st->decline
+ * FRT_ENCODE_NO_DEVICE).
+ */
+int frt_encode16_device(const double *rgba, int rgba_on_device, size_t width, size_t height, int mode, int device,
+                        const double srgb_max[3], const double inverse[3], const unsigned short code_one[3],
+                        unsigned char *out, uint32_t *und_idx, double *und_px, frt_encode_stats *st);
+
+/* copy `bytes` of device memory on `device` to the host (a declined device-resident canvas goes to the host pass) */
+int frt_encode_fetch(void *host, const void *device_ptr, size_t bytes, int device);
+
+/* message of this thread's last failing encode call */
+const char *frt_encode_error(void);
+
+/* free the encode's device buffers (kept between calls, per device) */
+void frt_encode_release(void);
+
+/*
+ * Diagnostics (current device): the device's 1.055 * pow(t, 1/2.4) - 0.055 against the host libm's on n values t:
+ * log-uniform over [0.0031308, 4], one in eight within 4 ulps of 1.0 and one in eight within 4 ulps of 0.0031308
+ * (from it upwards). Returns the number of lanes whose pow or sRGB value deviates from the host's by 2^-44
+ * relative or more (or is not finite), -1 on a HIP error. out[0] the worst relative deviation of the sRGB value,
+ * out[1] of pow alone, out[2] the lanes whose sRGB value differs at all (min(nout, 3) written; out may be NULL).
+ */
+int64_t frt_encode_selftest(int64_t n, uint64_t seed, double *out, int nout);
+
 #ifdef __cplusplus
 }
 #endif
