@@ -307,8 +307,9 @@ __device__ __forceinline__ bool prepare_node(const DevScene& S, const Batch& B, 
                                              NodeCols& rec,
                                              ShadowHead* __restrict__ heads, QueuedRay* __restrict__ next_q,
                                              unsigned long long* counters, unsigned* err, int64_t node, double* op,
-                                             int* spawned = nullptr) {
-    // this block's counter line: next-level queue segment count (word level + 1), pruned (16), hits (17)
+                                             int* spawned, int uniform_ok) {
+    // this block's counter line: next-level queue segment count (word level + 1), pruned (16), hits (17), waves
+    // on the uniform path (18)
     unsigned long long* line = counters + kCounterLine * (blockIdx.x % kQueueSegs);
     const int64_t seg_base = (int64_t)(blockIdx.x % kQueueSegs) * B.next_segcap;
 #ifdef FRT_WALK_PROF
@@ -346,7 +347,10 @@ __device__ __forceinline__ bool prepare_node(const DevScene& S, const Batch& B, 
         heads[node].material = -1;
         return false;
     }
-    Hit h{hr.t, -1, -1, hr.node};
+    // the rest per hit: on the scene as it is (leaf: the lane's own), or on its uniform view where every lane of the
+    // wave hit one leaf (leaf: that leaf, wave-uniform); the same operations in the same order either way
+    auto prepare_hit = [&](const DevScene& S, const int leaf) __attribute__((always_inline)) {
+    Hit h{hr.t, -1, -1, leaf};
     Comps c;
     prepare<kPat>(S, r, h, c);
     c.n1 = hn12 != nullptr ? hn12[2 * node] : 1.0;
@@ -458,9 +462,35 @@ __device__ __forceinline__ bool prepare_node(const DevScene& S, const Batch& B, 
     hd.key = key;
     hd.material = c.material;
     hd.pad = 0;
+#ifdef FRT_EXPERIMENT_HEAD_COLS
+    // (measurements only — wrong images: the head's five words stored as five columns of the same 40n bytes, word f
+    // of node i at word f * n + i, which nobody reads back as such: what k_prepare's time would be with a columnar
+    // ShadowHead, before any reader is changed; profiles/r07_ab_head_cols.txt)
+    {
+        uint64_t t[5];
+        __builtin_memcpy(t, &hd, sizeof(hd));
+        uint64_t* w = (uint64_t*)heads;
+#pragma unroll
+        for (int f = 0; f < 5; ++f) w[(int64_t)f * n + node] = t[f];
+    }
+#else
     heads[node] = hd;
+#endif
     PSTAMP(4);
     for (int k = 0; k < 3; ++k) op[k] = c.over_point[k];
+    };
+    // FRT_PREPARE_UNIFORM (default on): a wave whose lanes with a hit all hit one leaf (level 0 at 64 spp: a wave is
+    // a pixel's samples; the levels below run in parent order) looks the hit object up once, through the scalar
+    // cache; [18] counts those waves (statistics frames only)
+    if (uniform_ok) {
+        const int leaf_u = uniform(hr.node);
+        if (__ballot(hr.node != leaf_u) == 0ull) {
+            if (B.stats) wave_count(line + 18, (int)(threadIdx.x & 63) == __builtin_ctzll(__ballot(true)));
+            prepare_hit(uniform_view(S), leaf_u);
+            return true;
+        }
+    }
+    prepare_hit(S, hr.node);
     return true;
 }
 
@@ -506,7 +536,7 @@ k_prepare(DevScene S, Batch B, const QueuedRay* __restrict__ q, int64_t n, const
           const double* __restrict__ hn12,
           NodeCols rec, ShadowHead* __restrict__ heads, QueuedRay* __restrict__ next_q, unsigned long long* counters,
           unsigned* err, float* __restrict__ tbox, int tile_log2, float* __restrict__ stbox, int sub_log2,
-          int32_t* __restrict__ counts, unsigned long long* __restrict__ spawn_masks) {
+          int32_t* __restrict__ counts, unsigned long long* __restrict__ spawn_masks, int uniform_ok) {
     const int64_t node = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     double op[3] = {0.0, 0.0, 0.0};
     bool hit = false;
@@ -519,7 +549,7 @@ k_prepare(DevScene S, Batch B, const QueuedRay* __restrict__ q, int64_t n, const
     int spawned = 0;
     if (node < n)
         hit = prepare_node<kPat>(S, B, q, n, hits, hn12, rec, heads, next_q, counters, err, node, op,
-                                 spawn_masks != nullptr ? &spawned : nullptr);
+                                 spawn_masks != nullptr ? &spawned : nullptr, uniform_ok);
     if (spawn_masks != nullptr) {  // (every lane of the wave is here)
         const unsigned long long mr = __ballot(spawned & 1), mt = __ballot((spawned >> 1) & 1);
         const int64_t g = node >> 6, G = (n + 63) >> 6;
@@ -2257,6 +2287,7 @@ struct frt_scene_handle {
     frt::Light32 light32{nullptr, nullptr};
     int queue_sort = 2;                 // a level's queue in parent order (FRT_QUEUE_SORT: 2 dense, 1 sorted, 0 off)
     int queue_sort_shift = 0;           // (FRT_QUEUE_SORT_SHIFT)
+    int prepare_uniform = 1;            // k_prepare's scalar path for waves that hit one leaf (FRT_PREPARE_UNIFORM=0: off)
     uint32_t* qsort = nullptr;          // (its keys, their alternate buffer and the storage slots, 3 words per entry)
     int64_t qsort_cap = 0;
     unsigned long long* spawn_masks = nullptr;  // (FRT_QUEUE_SORT=2: the next level's taken slots, k_prepare)
@@ -2296,7 +2327,8 @@ struct frt_scene_handle {
     double* out_dev = nullptr;
     int64_t out_cap = 0;
     // kQueueSegs lines of kCounterLine words: [d] queue segment count of level d, [16] pruned,
-    // [17] shaded path nodes (per segment); line 0 [24] / [25]: photon store / photon queue
+    // [17] shaded path nodes, [18] k_prepare waves on the uniform path (per segment); line 0 [24] / [25]: photon
+    // store / photon queue
     unsigned long long* counters = nullptr;
     unsigned* err = nullptr;
     hipEvent_t ev[2] = {nullptr, nullptr};
@@ -3548,6 +3580,10 @@ int frt_scene_upload(const frt_scene* sc, int device, frt_scene_handle** out) {
         h->queue_sort = qs ? std::atoi(qs) : 2;
         const char* qsh = std::getenv("FRT_QUEUE_SORT_SHIFT");  // (A/B runs: parents' low bits out of the key)
         h->queue_sort_shift = qsh ? std::max(0, std::min(16, std::atoi(qsh))) : 0;
+        // k_prepare: a wave whose lanes all hit one leaf reads that leaf's node, transforms and material through the
+        // scalar cache (frt_shade.hpp uniform_view). FRT_PREPARE_UNIFORM=0: every wave per lane (A/B runs, tests)
+        const char* pu = std::getenv("FRT_PREPARE_UNIFORM");
+        h->prepare_uniform = pu && std::atoi(pu) == 0 ? 0 : 1;
     }
     // path-node keys carry a 12-bit heap code (k_prepare: children 2c, 2c + 1 of code c, root 1) and
     // the per-segment counter lines hold the level queue counts in words 0..15: a path of length L
@@ -5207,7 +5243,8 @@ static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* 
                 hipLaunchKernelGGL(h->S.num_patterns > 0 ? k_prepare<true> : k_prepare<false>, dim3(grid_for(n)),
                                    dim3(kBlock), 0, h->stream, h->S, B, q, n, h->hits, hn12,
                                    L.rec, L.head, N.q, h->counters, h->err, tiles ? h->tbox : nullptr, tl,
-                                   subtiles ? h->stbox : nullptr, stl, L.counts, dense ? h->spawn_masks : nullptr);
+                                   subtiles ? h->stbox : nullptr, stl, L.counts, dense ? h->spawn_masks : nullptr,
+                                   h->prepare_uniform);
                 FRT_HIP(hipGetLastError());
                 if (dense) {
                     hipcub::CountingInputIterator<int64_t> idx(0);
@@ -5438,11 +5475,13 @@ static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* 
         float ms = 0.f;
         (void)hipEventElapsedTime(&ms, h->ev[0], h->ev[1]);
         st->render_ms = ms;
-        uint64_t pruned = 0, hits = 0;
+        uint64_t pruned = 0, hits = 0, uniform_waves = 0;
         for (int j = 0; j < kQueueSegs; ++j) {
             pruned += host_counters[(size_t)j * kCounterLine + 16];
             hits += host_counters[(size_t)j * kCounterLine + 17];
+            uniform_waves += host_counters[(size_t)j * kCounterLine + 18];
         }
+        st->prepare_uniform_waves = uniform_waves;
         st->pruned_secondary = pruned;
         st->hits = hits;
         st->shadow_rays = h->S.cfg.include_direct ? hits * (uint64_t)h->samples_per_node : 0;

@@ -11,6 +11,27 @@
 
 namespace frt {
 
+// ---- the scene for a wave whose lanes all hit one leaf ----
+// The tables the hit object is looked up in (nodes, xchain, xforms, prim, materials) behind constant-address-space
+// pointers. They are read-only during a render; the address space tells the compiler so, and a load of them at a
+// wave-uniform index (a readfirstlane'd leaf and what is loaded through it) then goes through the scalar cache into
+// SGPRs: a 3x4 transform in two scalar loads instead of six vector loads per lane, the leaf-type switch and the
+// material tests scalar branches. The same functions run on this view as on the scene itself (same operations, same
+// order); at a lane-varying index its loads are the vector loads they were.
+template <class T>
+__device__ __forceinline__ const T* const_table(const T* p) {
+    return (const T*)(const __attribute__((address_space(4))) T*)(uint64_t)p;
+}
+__device__ __forceinline__ DevScene uniform_view(const DevScene& S) {
+    DevScene U = S;
+    U.nodes = const_table(S.nodes);
+    U.xchain = const_table(S.xchain);
+    U.xforms = const_table(S.xforms);
+    U.prim = const_table(S.prim);
+    U.materials = const_table(S.materials);
+    return U;
+}
+
 // ---- transform chains (nearest transformed ancestors, tparent links) ----
 __device__ __forceinline__ int first_xf(const DevScene& S, int leaf) {
     return S.nodes[leaf].xform >= 0 ? leaf : S.nodes[leaf].tparent;

@@ -46,7 +46,8 @@ class FrameStats(ctypes.Structure):
                 ("shadow_tile_mixed", ctypes.c_uint64), ("shadow_pairs", ctypes.c_uint64),
                 ("shadow_pairs_mixed", ctypes.c_uint64), ("shadow_sub_pairs", ctypes.c_uint64),
                 ("shadow_sub_mixed", ctypes.c_uint64), ("shadow_subtile_pairs", ctypes.c_uint64),
-                ("shadow_subtile_mixed", ctypes.c_uint64), ("lit_nodes", ctypes.c_uint64)]
+                ("shadow_subtile_mixed", ctypes.c_uint64), ("lit_nodes", ctypes.c_uint64),
+                ("prepare_uniform_waves", ctypes.c_uint64)]
 
     def as_dict(self) -> dict:
         names = ["trace", "shadow", "shade", "combine", "resolve", "trace_primary", "prepare", "gi"]
@@ -70,6 +71,7 @@ class FrameStats(ctypes.Structure):
             "shadow_sub_pairs": int(self.shadow_sub_pairs), "shadow_sub_mixed": int(self.shadow_sub_mixed),
             "shadow_subtile_pairs": int(self.shadow_subtile_pairs),
             "shadow_subtile_mixed": int(self.shadow_subtile_mixed), "lit_nodes": int(self.lit_nodes),
+            "prepare_uniform_waves": int(self.prepare_uniform_waves),
         }
 
 

@@ -249,6 +249,8 @@ typedef struct frt_frame_stats {
     uint64_t shadow_subtile_mixed; /* of those, the ones whose nodes frt_jit_beam_list tested */
     uint64_t lit_nodes;           /* path nodes some light sample reaches (k_shade_lit's lanes); counted per frame
                                      when stats are asked for */
+    uint64_t prepare_uniform_waves; /* k_prepare waves whose lanes all hit one leaf and took the scalar path
+                                       (FRT_PREPARE_UNIFORM); counted in statistics frames only */
 } frt_frame_stats;
 
 /* number of HIP devices visible (0 when no GPU) */

@@ -8,5 +8,5 @@ mkdir -p "$R/variants"
 python3 -c "import sys; sys.path.insert(0, '$R'); from fast_ray_tracer_amd import build as b; b.write_jit_embed()"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -I"$R/include" \
     -I"$R/fast_ray_tracer_amd/csrc" "$@" -o "$R/variants/$NAME.so" "$R/fast_ray_tracer_amd/csrc/frt_engine.hip" \
-    "$R/fast_ray_tracer_amd/csrc/frt_jit.hip" -lhiprtc
+    "$R/fast_ray_tracer_amd/csrc/frt_jit.hip" "$R/fast_ray_tracer_amd/csrc/frt_encode.hip" -lhiprtc
 echo "$R/variants/$NAME.so"
