@@ -640,6 +640,43 @@ __device__ __forceinline__ void camera_eyev(const DevScene& S, const Batch& B, i
     for (int k = 0; k < 3; ++k) eyev[k] = r.d[k] * -1.0;
 }
 
+// Level 0 of a strip of views (frt_render_views*): the strip's pixels are the views' pixels one view after the
+// other (view_pixels each, in render order), and sample i of the batch gets the camera ray its view's camera_ray
+// gives it as a frame of its own, key included, written as a queued ray (parent -1, slot 0: what k_prepare takes
+// for a level-0 node). The level then runs as every other level does, from its queue: k_trace, frt_jit_trace,
+// k_prepare and the shading kernels are the single-view ones, and the views enter nowhere else. The camera table
+// sits behind a constant-address-space pointer (frt_shade.hpp const_table): a wave whose lanes share a view reads
+// its camera once, through the scalar cache; a wave that straddles two views loads per lane.
+__global__ void __launch_bounds__(kBlock) k_view_rays(DevScene S, Batch B, const frt_camera* __restrict__ cams,
+                                                      int32_t nviews, int64_t view_pixels, int64_t n,
+                                                      QueuedRay* __restrict__ q, unsigned* err) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t pix = B.pixel_begin + i / B.spp;
+    const int view = (int)min((int64_t)(nviews - 1), pix / view_pixels);
+    Batch Bv = B;  // (camera_ray's pixel of sample i: Bv.pixel_begin + i / spp = the pixel inside the view)
+    Bv.pixel_begin = pix - (int64_t)view * view_pixels - i / B.spp;
+    unsigned e = 0;
+    auto emit = [&](const frt_camera& cam) {
+        DevScene Sv = S;
+        Sv.cam = cam;
+        QueuedRay qr;
+        Ray r;
+        camera_ray(Sv, Bv, i, r, qr.key, e);
+        for (int k = 0; k < 3; ++k) {
+            qr.o[k] = r.o[k];
+            qr.d[k] = r.d[k];
+        }
+        qr.parent = -1;
+        qr.slot = 0;
+        q[i] = qr;
+    };
+    const int view_u = uniform(view);
+    if (__ballot(view != view_u) == 0ull) emit(const_table(cams)[view_u]);
+    else emit(cams[view]);
+    if (e) atomicOr(err, e);
+}
+
 // lighting_microfacet (renderer.c:895-979) per light, summed as shade_hit does (renderer.c:704-725): the
 // A, D, S triples of path node i into out (out[4k + c]: term k, channel c)
 // (lds_row: k_shade_lit's per-wave LDS staging of a multi-row light's row, kLdsPoints points; nullptr elsewhere)
@@ -2208,6 +2245,7 @@ struct frt_scene_handle {
     int device = 0;
     frt::DevScene S{};
     std::vector<void*> owned;
+    std::vector<double> host_table;  // the non-jittered CMJ table on the device (frt_scene_set_camera compares it)
     hipStream_t stream = nullptr;
     // light-sample lookup for k_shadow
     int32_t* j_light = nullptr;
@@ -2326,6 +2364,12 @@ struct frt_scene_handle {
     int64_t sample_cap = 0;
     double* out_dev = nullptr;
     int64_t out_cap = 0;
+    // a strip of views (frt_render_views*): the frame's camera table and its level-0 rays (k_view_rays)
+    frt_camera* view_cams = nullptr;
+    int64_t view_cams_cap = 0;
+    int32_t strip_views = 0;  // views of the frame being rendered (0: a frame of the handle's own camera)
+    frt::QueuedRay* view_q = nullptr;
+    int64_t view_q_cap = 0;
     // kQueueSegs lines of kCounterLine words: [d] queue segment count of level d, [16] pruned,
     // [17] shaded path nodes, [18] k_prepare waves on the uniform path (per segment); line 0 [24] / [25]: photon
     // store / photon queue
@@ -3315,6 +3359,8 @@ int frt_scene_upload(const frt_scene* sc, int device, frt_scene_handle** out) {
     S.lights = upload(h, sc->lights, (size_t)sc->num_lights, rc);
     S.light_points = upload(h, sc->light_points, (size_t)sc->light_point_len, rc);
     S.sample_table = upload(h, sc->sample_table, (size_t)(2 * sc->camera.usteps * sc->camera.vsteps), rc);
+    if (S.sample_table != nullptr)
+        h->host_table.assign(sc->sample_table, sc->sample_table + 2 * sc->camera.usteps * sc->camera.vsteps);
     {
         // per node: does the leaf's material cast shadows (read by the shadow walk)
         std::vector<uint8_t> casts((size_t)std::max(1, sc->num_nodes), 0);
@@ -3731,6 +3777,8 @@ void frt_scene_release(frt_scene_handle* h) {
     }
     hip_ignore(hipFree(h->sample_col.w));
     hip_ignore(hipFree(h->out_dev));
+    hip_ignore(hipFree(h->view_cams));
+    hip_ignore(hipFree(h->view_q));
     hip_ignore(hipFree(h->counters));
     hip_ignore(hipFree(h->shade_lit));
     hip_ignore(hipFree(h->shade_lcount));
@@ -3756,6 +3804,13 @@ void frt_scene_release(frt_scene_handle* h) {
     delete h;
 }
 
+// level 0 leaves eyev to camera_eyev (NodeCols::eye_cam) without GI, and never in a strip of views, whose shading
+// kernels then need no camera at all (FRT_EYE_CAM=0: level 0 stores eyev too, A/B runs)
+static int32_t level_eye_cam(const frt_scene_handle* h, size_t d) {
+    static const bool eye_cam_env = !(std::getenv("FRT_EYE_CAM") && std::atoi(std::getenv("FRT_EYE_CAM")) == 0);
+    return d == 0 && !h->S.cfg.use_gi && eye_cam_env && h->strip_views == 0 ? 1 : 0;
+}
+
 static int ensure_level(frt_scene_handle* h, size_t d, int64_t need) {
     auto& L = h->levels[d];
     if (need <= L.cap) return 0;
@@ -3779,9 +3834,7 @@ static int ensure_level(frt_scene_handle* h, size_t d, int64_t need) {
         FRT_HIP(hipMalloc(&p, frt::NodeCols::bytes(nc)));
         L.rec.set((uint64_t*)p, nc);
         L.rec.root = d == 0 ? 1 : 0;
-        // (FRT_EYE_CAM=0: level 0 stores eyev too, A/B runs)
-        static const bool eye_cam_env = !(std::getenv("FRT_EYE_CAM") && std::atoi(std::getenv("FRT_EYE_CAM")) == 0);
-        L.rec.eye_cam = d == 0 && !h->S.cfg.use_gi && eye_cam_env ? 1 : 0;
+        L.rec.eye_cam = level_eye_cam(h, d);
     }
     FRT_HIP(hipMalloc((void**)&L.head, nc * sizeof(frt::ShadowHead)));
     L.rec.head = L.head;
@@ -5108,6 +5161,23 @@ static int render_impl(frt_scene_handle* h, const frt_frame_params* P, double* d
     return rc;
 }
 
+// a strip frame: the views' shared size and steps stand in for the handle's camera while it renders (the frame
+// reads hsize and the steps from it; the rays come from the camera table), and the handle's camera is back after it
+static int render_strip(frt_scene_handle* h, const frt_camera* cams, int32_t nviews, const frt_frame_params* P,
+                        double* dev_out, frt_frame_stats* st) {
+    FRT_HIP(hipSetDevice(h->device));
+    if (grow(&h->view_cams, h->view_cams_cap, nviews)) return -1;
+    FRT_HIP(hipMemcpy(h->view_cams, cams, (size_t)nviews * sizeof(frt_camera), hipMemcpyHostToDevice));
+    const frt_camera own = h->S.cam;
+    h->S.cam = cams[0];
+    h->strip_views = nviews;
+    const int rc = render_impl(h, P, dev_out, st);
+    h->strip_views = 0;
+    h->S.cam = own;
+    if (!h->levels.empty()) h->levels[0].rec.eye_cam = level_eye_cam(h, 0);
+    return rc;
+}
+
 static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* dev_out, frt_frame_stats* st) {
     using namespace frt;
     FRT_HIP(hipSetDevice(h->device));
@@ -5117,7 +5187,10 @@ static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* 
     const int64_t stride = P->row_stride > 0 ? P->row_stride : 1;
     int64_t nrows = 0;
     for (int64_t r = P->row_begin; r < P->row_end; r += stride) nrows++;
-    const int64_t npix = nrows * hs;
+    // a strip of views: the views' rows one view after the other (nrows each), level 0 from k_view_rays' queue
+    const int32_t nviews = h->strip_views;
+    const int64_t npix = nrows * hs * std::max(1, nviews);
+    if (!h->levels.empty()) h->levels[0].rec.eye_cam = level_eye_cam(h, 0);
     const int32_t spp = (int32_t)(h->S.cam.usteps * h->S.cam.vsteps);
     if (spp <= 0) return fail("render: usteps*vsteps must be positive");
     // 8 M samples unless the caller asks for more. Each batch pays the shadow pass's host round trips (the list
@@ -5178,10 +5251,11 @@ static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* 
             h->sample_col.cap = h->sample_cap = ns;
         }
         if (ensure_level(h, 0, ns)) return -1;
+        if (nviews > 0 && grow(&h->view_q, h->view_q_cap, ns)) return -1;
         Batch B{};
         B.sample_begin = 0;
-        // global sample index of the first sample: pixel (row, col) in frame coordinates
-        const int64_t first_row = P->row_begin + (p0 / hs) * stride;
+        // global sample index of the first sample: pixel (row, col) in frame coordinates (a strip: in its view's)
+        const int64_t first_row = P->row_begin + ((p0 / hs) % std::max<int64_t>(1, nrows)) * stride;
         B.sample_begin = (first_row * hs + p0 % hs) * spp;
         B.pixel_begin = p0;
         B.num_samples = ns;
@@ -5213,10 +5287,15 @@ static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* 
             if (grow(&h->hits, h->hits_cap, n)) return -1;
             if (!h->S.cfg.all_ni_one && grow(&h->hn12, h->hn12_cap, 2 * n)) return -1;
             double* hn12 = h->S.cfg.all_ni_one ? nullptr : h->hn12;
-            const QueuedRay* q = d == 0 ? nullptr : L.q;
+            const QueuedRay* q = d == 0 ? (nviews > 0 ? h->view_q : nullptr) : L.q;
             bool dense = false;
             {
                 KTimer t(h, st, d == 0 ? 5 : 0);
+                if (d == 0 && nviews > 0) {
+                    hipLaunchKernelGGL(k_view_rays, dim3(grid_for(n)), dim3(kBlock), 0, h->stream, h->S, B,
+                                       (const frt_camera*)h->view_cams, nviews, nrows * hs, n, h->view_q, h->err);
+                    FRT_HIP(hipGetLastError());
+                }
                 launch_trace(h, B, q, n, h->hits, 0, hn12, true);
                 FRT_HIP(hipGetLastError());
             }
@@ -5519,6 +5598,107 @@ static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* 
         std::snprintf(buf, sizeof(buf), "render: device error bits 0x%x", err);
         return fail(buf);
     }
+    return 0;
+}
+
+// what a camera must satisfy before a frame indexes with it (frt_scene_set_camera, frt_render_views*): positive
+// sizes and steps, a sample count per pixel the batches hold in 32 bits, and a sample count per frame whose path-node
+// keys (global sample << 12 | heap code, frt_camera.hpp camera_ray) fit 64 bits
+static int check_camera(const char* who, const frt_camera* cam) {
+    const std::string w(who);
+    if (cam->hsize <= 0 || cam->vsize <= 0)
+        return fail(w + ": hsize and vsize must be positive (got " + std::to_string(cam->hsize) + " x " +
+                    std::to_string(cam->vsize) + ")");
+    if (cam->usteps <= 0 || cam->vsteps <= 0)
+        return fail(w + ": usteps and vsteps must be positive (got " + std::to_string(cam->usteps) + " x " +
+                    std::to_string(cam->vsteps) + ")");
+    const int64_t kMaxSamples = (int64_t)1 << 52;
+    if (cam->usteps > INT32_MAX / cam->vsteps)
+        return fail(w + ": usteps * vsteps = " + std::to_string(cam->usteps) + " * " + std::to_string(cam->vsteps) +
+                    " samples per pixel are more than the engine indexes (2^31 - 1)");
+    const int64_t spp = cam->usteps * cam->vsteps;
+    if (cam->hsize > kMaxSamples / spp || cam->vsize > kMaxSamples / spp / cam->hsize)
+        return fail(w + ": " + std::to_string(cam->hsize) + " x " + std::to_string(cam->vsize) + " pixels of " +
+                    std::to_string(spp) + " samples are more samples per frame than the engine indexes (2^52)");
+    return 0;
+}
+
+int frt_scene_set_camera(frt_scene_handle* h, const frt_camera* cam, const double* sample_table) {
+    if (!h || !cam) return fail("frt_scene_set_camera: null argument");
+    if (check_camera("frt_scene_set_camera", cam)) return -1;
+    if (!sample_table) return fail("frt_scene_set_camera: null sample table");
+    const size_t nt = (size_t)(2 * cam->usteps * cam->vsteps);
+    if (h->host_table.size() != nt || std::memcmp(h->host_table.data(), sample_table, nt * sizeof(double)) != 0) {
+        // a table of its own beside the old one, which goes only once the new one is on the device: a failure
+        // here leaves the handle as it was (no frame is in flight: every frame ends with a stream synchronize)
+        FRT_HIP(hipSetDevice(h->device));
+        void* p = nullptr;
+        FRT_HIP(hipMalloc(&p, nt * sizeof(double)));
+        const hipError_t e = hipMemcpy(p, sample_table, nt * sizeof(double), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            hip_ignore(hipFree(p));
+            return fail(std::string("frt_scene_set_camera: hipMemcpy: ") + hipGetErrorString(e));
+        }
+        void* old = (void*)h->S.sample_table;
+        auto at = old != nullptr ? std::find(h->owned.begin(), h->owned.end(), old) : h->owned.end();
+        if (at != h->owned.end()) {
+            *at = p;
+            hip_ignore(hipFree(old));
+        } else {
+            h->owned.push_back(p);
+        }
+        h->S.sample_table = (const double*)p;
+        h->host_table.assign(sample_table, sample_table + nt);
+    }
+    h->S.cam = *cam;
+    return 0;
+}
+
+// the views of a strip: each a camera a frame may index with, all of one size, steps and jitter, the steps the
+// handle's own (its sample table is the strip's)
+static int check_views(const char* who, const frt_scene_handle* h, const frt_camera* cams, int32_t nviews) {
+    const std::string w(who);
+    if (nviews <= 0) return fail(w + ": the number of views must be positive (got " + std::to_string(nviews) + ")");
+    for (int32_t k = 0; k < nviews; ++k) {
+        if (check_camera(who, cams + k)) return -1;
+        const frt_camera &a = cams[0], &b = cams[k];
+        if (a.hsize != b.hsize || a.vsize != b.vsize)
+            return fail(w + ": view " + std::to_string(k) + " is " + std::to_string(b.hsize) + " x " +
+                        std::to_string(b.vsize) + ", view 0 " + std::to_string(a.hsize) + " x " +
+                        std::to_string(a.vsize) + ": the views of a strip share one size");
+        if (a.usteps != b.usteps || a.vsteps != b.vsteps || a.jitter != b.jitter)
+            return fail(w + ": view " + std::to_string(k) + " has steps " + std::to_string(b.usteps) + " x " +
+                        std::to_string(b.vsteps) + " jitter " + std::to_string(b.jitter) + ", view 0 " +
+                        std::to_string(a.usteps) + " x " + std::to_string(a.vsteps) + " jitter " +
+                        std::to_string(a.jitter) + ": the views of a strip share their steps and jitter");
+    }
+    if (cams[0].usteps != h->S.cam.usteps || cams[0].vsteps != h->S.cam.vsteps)
+        return fail(w + ": the views' steps " + std::to_string(cams[0].usteps) + " x " + std::to_string(cams[0].vsteps) +
+                    " are not the handle's " + std::to_string(h->S.cam.usteps) + " x " +
+                    std::to_string(h->S.cam.vsteps) + " (its sample table): frt_scene_set_camera one of them first");
+    return 0;
+}
+
+int frt_render_views_device(frt_scene_handle* h, const frt_camera* cams, int32_t nviews, const frt_frame_params* P,
+                            double* device_rgba, frt_frame_stats* st) {
+    if (!h || !cams || !P || !device_rgba) return fail("frt_render_views_device: null argument");
+    if (check_views("frt_render_views_device", h, cams, nviews)) return -1;
+    return render_strip(h, cams, nviews, P, device_rgba, st);
+}
+
+int frt_render_views_host(frt_scene_handle* h, const frt_camera* cams, int32_t nviews, const frt_frame_params* P,
+                     double* host_rgba, frt_frame_stats* st) {
+    if (!h || !cams || !P || !host_rgba) return fail("frt_render_views_host: null argument");
+    if (check_views("frt_render_views_host", h, cams, nviews)) return -1;
+    FRT_HIP(hipSetDevice(h->device));
+    const int64_t stride = P->row_stride > 0 ? P->row_stride : 1;
+    int64_t nrows = 0;
+    for (int64_t r = P->row_begin; r < P->row_end; r += stride) nrows++;
+    const int64_t n = (int64_t)nviews * nrows * cams[0].hsize * 4;
+    if (grow(&h->out_dev, h->out_cap, std::max<int64_t>(n, 4))) return -1;
+    const int rc = render_strip(h, cams, nviews, P, h->out_dev, st);
+    if (rc) return rc;
+    FRT_HIP(hipMemcpy(host_rgba, h->out_dev, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -31,7 +31,9 @@
  * page-locked (frt_canvas_alloc_pinned), 0 when malloc'd. render_multi's canvas is page-locked so that the device's
  * copy of the frame is one DMA into it (into malloc'd memory the runtime stages it through its own buffers, and a
  * fresh 66 MB array at 1920x1080 first takes ~16 000 page faults); canvas_free hands such an array to a one-entry
- * pool that the next render_multi of the same size takes again.
+ * pool that the next render_multi of the same size takes again. Page-locked memory is a scarce kind: at most
+ * FRT_PINNED_CANVASES (default 4) such arrays are out in live canvases at once, and a canvas asked for beyond that
+ * (a camera loop that keeps every frame) gets an ordinary malloc'd array, as canvas_alloc gives.
  */
 typedef struct {
     struct canvas c;
@@ -41,6 +43,14 @@ typedef struct {
 static pthread_mutex_t g_pool_lock = PTHREAD_MUTEX_INITIALIZER;
 static void *g_pool_arr;     /* an idle page-locked array */
 static size_t g_pool_bytes;
+static size_t g_pinned_out;  /* page-locked arrays held by live canvases */
+
+static size_t
+pinned_cap(void)
+{
+    const char *e = getenv("FRT_PINNED_CANVASES");
+    return e != NULL && *e ? (size_t)strtoul(e, NULL, 10) : 4;
+}
 
 static Canvas
 canvas_new(size_t width, size_t height, bool super_sample, void (*color_space_fn)(const Color, Color))
@@ -77,8 +87,12 @@ frt_canvas_alloc_pinned(size_t width, size_t height, bool super_sample, void (*c
     }
     const size_t bytes = width * height * sizeof(Color);
     void *stale = NULL;
+    const size_t cap = pinned_cap();
     pthread_mutex_lock(&g_pool_lock);
-    if (g_pool_arr != NULL && g_pool_bytes == bytes) {
+    const int over = g_pinned_out >= cap;
+    if (over) {
+        /* (the pool's idle array stays for the next canvas under the cap) */
+    } else if (g_pool_arr != NULL && g_pool_bytes == bytes) {
         c->arr = (Color *)g_pool_arr;
         g_pool_arr = NULL;
     } else {
@@ -87,15 +101,25 @@ frt_canvas_alloc_pinned(size_t width, size_t height, bool super_sample, void (*c
     }
     pthread_mutex_unlock(&g_pool_lock);
     frt_host_pinned_free(stale);
-    if (c->arr == NULL) {
+    if (c->arr == NULL && !over) {
         c->arr = (Color *)frt_host_pinned_alloc(bytes);
     }
     if (c->arr != NULL) {
         ((canvas_box *)c)->pinned_bytes = bytes;
+        pthread_mutex_lock(&g_pool_lock);
+        ++g_pinned_out;
+        pthread_mutex_unlock(&g_pool_lock);
     } else {
         c->arr = (Color *)malloc(bytes);  /* (no page-locked memory: an ordinary array) */
     }
     return c;
+}
+
+/* diagnostics: 1 when the canvas's array is page-locked (counts towards FRT_PINNED_CANVASES), 0 when malloc'd */
+int
+frt_canvas_is_pinned(Canvas c)
+{
+    return c != NULL && ((canvas_box *)c)->pinned_bytes > 0;
 }
 
 void
@@ -128,6 +152,7 @@ canvas_free(Canvas c)
     if (b->pinned_bytes > 0) {
         void *spill = c->arr;
         pthread_mutex_lock(&g_pool_lock);
+        --g_pinned_out;
         if (g_pool_arr == NULL) {
             g_pool_arr = c->arr;
             g_pool_bytes = b->pinned_bytes;

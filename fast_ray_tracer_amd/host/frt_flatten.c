@@ -375,6 +375,48 @@ warm_bounds(Shape s)
 }
 
 int
+frt_flatten_camera(Camera cam, size_t usteps, size_t vsteps, bool jitter, frt_camera *fc, double **table_out)
+{
+    memset(fc, 0, sizeof(*fc));
+    *table_out = NULL;
+    fc->hsize = (int64_t)cam->hsize;
+    fc->vsize = (int64_t)cam->vsize;
+    fc->usteps = (int64_t)usteps;
+    fc->vsteps = (int64_t)vsteps;
+    fc->half_width = cam->half_width;
+    fc->half_height = cam->half_height;
+    fc->pixel_size = cam->pixel_size;
+    fc->canvas_distance = cam->canvas_distance;
+    memcpy(fc->inv, cam->transform_inverse, sizeof(fc->inv));
+    fc->aperture_size = cam->aperture.size;
+    fc->aperture_type = (int32_t)cam->aperture.type;
+    fc->jitter = jitter ? 1 : 0;
+    fc->aperture_args[0] = cam->aperture.u.cross.x1;
+    fc->aperture_args[1] = cam->aperture.u.cross.x2;
+    fc->aperture_args[2] = cam->aperture.u.cross.y1;
+    fc->aperture_args[3] = cam->aperture.u.cross.y2;
+    if (usteps == 0 || vsteps == 0) {
+        return 0;  /* (no table: the engine refuses such a camera with the reason) */
+    }
+
+    /* the non-jittered CMJ sub-pixel table every pixel uses (renderer.c:145-151) */
+    struct sampler smp;
+    sampler_2d(false, usteps, vsteps, sampler_default_constraint, &smp);
+    double *table = (double *)malloc(2 * usteps * vsteps * sizeof(double));
+    if (table != NULL) {
+        for (size_t v = 0; v < vsteps; ++v) {
+            for (size_t u = 0; u < usteps; ++u) {
+                size_t idx[2] = {u, v};
+                sampler_get_point_2d(&smp, idx, table + 2 * (v * usteps + u));
+            }
+        }
+    }
+    sampler_free(&smp);
+    *table_out = table;
+    return table != NULL ? 0 : -1;
+}
+
+int
 frt_flatten_scene(Camera cam, World w, size_t usteps, size_t vsteps, bool jitter, frt_scene *out,
                   char *err, size_t errlen)
 {
@@ -477,35 +519,15 @@ frt_flatten_scene(Camera cam, World w, size_t usteps, size_t vsteps, bool jitter
     out->light_point_len = (int64_t)(3 * at);
     out->light_points = pts;
 
-    frt_camera *fc = &out->camera;
-    fc->hsize = (int64_t)cam->hsize;
-    fc->vsize = (int64_t)cam->vsize;
-    fc->usteps = (int64_t)usteps;
-    fc->vsteps = (int64_t)vsteps;
-    fc->half_width = cam->half_width;
-    fc->half_height = cam->half_height;
-    fc->pixel_size = cam->pixel_size;
-    fc->canvas_distance = cam->canvas_distance;
-    memcpy(fc->inv, cam->transform_inverse, sizeof(fc->inv));
-    fc->aperture_size = cam->aperture.size;
-    fc->aperture_type = (int32_t)cam->aperture.type;
-    fc->jitter = jitter ? 1 : 0;
-    fc->aperture_args[0] = cam->aperture.u.cross.x1;
-    fc->aperture_args[1] = cam->aperture.u.cross.x2;
-    fc->aperture_args[2] = cam->aperture.u.cross.y1;
-    fc->aperture_args[3] = cam->aperture.u.cross.y2;
-
-    /* the non-jittered CMJ sub-pixel table every pixel uses (renderer.c:145-151) */
-    struct sampler smp;
-    sampler_2d(false, usteps, vsteps, sampler_default_constraint, &smp);
-    double *table = (double *)malloc(2 * usteps * vsteps * sizeof(double));
-    for (size_t v = 0; v < vsteps; ++v) {
-        for (size_t u = 0; u < usteps; ++u) {
-            size_t idx[2] = {u, v};
-            sampler_get_point_2d(&smp, idx, table + 2 * (v * usteps + u));
-        }
+    double *table = NULL;
+    if (frt_flatten_camera(cam, usteps, vsteps, jitter, &out->camera, &table)) {
+        snprintf(err, errlen, "out of host memory for the camera's sample table");
+        pm_free(&c.mat_map);
+        pm_free(&c.pat_map);
+        pm_free(&c.tex_map);
+        frt_flat_scene_free(out);
+        return -1;
     }
-    sampler_free(&smp);
     out->sample_table = table;
 
     const struct illumination_config *ic = &w->global_config->illumination;

@@ -19,6 +19,12 @@
  *   FRT_PRECISION=fast32|parity   the frame's shading precision (the engine reads it at every frame; default
  *                          parity; include/frt_device.h enum frt_precision). As an FRT_* variable it is part of
  *                          knob_signature, so a change of mode does not reuse the kept handles
+ *   FRT_RM_KEEP=0          release the handles at the end of each call (default: kept for the next call with the
+ *                          same world, whose camera they take if it differs: kept_take_camera)
+ *   FRT_PINNED_CANVASES=<n> page-locked canvases out at once (default 4; host/frt_canvas.c)
+ *
+ * Beside render_multi: frt_render_views (n cameras of one size in one strip frame), frt_camera_look_at and
+ * frt_host_set_camera (the camera of a resident handle moved); INTEGRATION.md "Views".
  *
  * The frt_capture_* functions let a harness compile an unmodified generated
  * main.c with -Drender_multi=frt_capture_render_multi to obtain the built
@@ -26,6 +32,7 @@
  * bench.py).
  */
 #include <pthread.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -103,6 +110,69 @@ frt_host_prepare(Camera cam, World w, size_t usteps, size_t vsteps, bool jitter,
     frt_encode_note_device(device);
     return h;
 }
+
+/*
+ * Move the camera of a resident handle (frt_host_prepare's, or any frt_scene_upload's): cam flattened with the render
+ * call's steps and jitter (frt_flatten_camera) replaces the handle's camera (frt_scene_set_camera); the world on the
+ * device, its kernels, level state and photon maps stay. Returns 0, or -1 with the reason in frt_host_last_error
+ * (the handle then keeps its old camera).
+ */
+int
+frt_host_set_camera(frt_scene_handle *h, Camera cam, size_t usteps, size_t vsteps, bool jitter)
+{
+    g_host_error[0] = '\0';
+    if (h == NULL || cam == NULL) {
+        snprintf(g_host_error, sizeof(g_host_error), "null handle / camera");
+        return -1;
+    }
+    frt_camera fc;
+    double *table = NULL;
+    if (frt_flatten_camera(cam, usteps, vsteps, jitter, &fc, &table)) {
+        snprintf(g_host_error, sizeof(g_host_error), "out of host memory for the camera's sample table");
+        return -1;
+    }
+    const double none[2] = {0.5, 0.5};
+    const int rc = frt_scene_set_camera(h, &fc, table != NULL ? table : none);
+    free(table);
+    if (rc) {
+        snprintf(g_host_error, sizeof(g_host_error), "%s", frt_last_error());
+        return -1;
+    }
+    return 0;
+}
+
+/*
+ * A camera at `from` looking at `to`, built as a generated main() builds its own (view_transform, then camera():
+ * the reference's operation order, so the values written in a scene's main.c give that scene's camera bit for bit)
+ * with the aperture and steps of `like`. The aperture is copied as a value: its sampler's tables stay `like`'s, so
+ * the camera is released with free() and must not outlive `like`. NULL when out of memory or `like` is NULL.
+ */
+Camera
+frt_camera_look_at(const double from[3], const double to[3], const double up[3], size_t hsize, size_t vsize, double fov,
+                   double distance, Camera like)
+{
+    if (like == NULL || from == NULL || to == NULL || up == NULL) {
+        return NULL;
+    }
+    Point f = {from[0], from[1], from[2], 1.0}, t = {to[0], to[1], to[2], 1.0};
+    Vector u = {up[0], up[1], up[2], 0.0};
+    Matrix xform;
+    view_transform(f, t, u, xform);
+    struct aperture ap = like->aperture;
+    return camera(hsize, vsize, fov, distance, like->usteps, like->vsteps, &ap, xform);
+}
+
+/* where a flattened scene keeps its camera and table, and the camera's size, for bindings that read them back */
+size_t frt_scene_camera_offset(void) { return offsetof(frt_scene, camera); }
+size_t frt_scene_table_offset(void) { return offsetof(frt_scene, sample_table); }
+size_t frt_camera_size(void) { return sizeof(frt_camera); }
+
+/* accessors for bindings (runtime.py Scene.view): a captured camera's scalars, a view's aperture size, its release */
+double frt_camera_fov(Camera c) { return c->field_of_view; }
+double frt_camera_distance(Camera c) { return c->canvas_distance; }
+double frt_camera_aperture_size(Camera c) { return c->aperture.size; }
+void frt_camera_set_aperture_size(Camera c, double size) { c->aperture.size = size; }
+void frt_camera_free(Camera c) { free(c); }
 
 static void
 write_stats(const char *path, const frt_frame_stats *st, Camera cam, size_t usteps, size_t vsteps, int ndev)
@@ -247,10 +317,11 @@ device_worker(void *arg)
 
 /*
  * The handles of the last render_multi stay alive (FRT_RM_KEEP=0: released at once, as before): a later call
- * with the same flattened scene on the same devices renders on them without uploading the scene, compiling or
- * loading its kernels or allocating the level state again, and the one call a generated main() makes does not
- * wait for the release (the process's exit frees the device memory, as it frees the reference's per-thread
- * world copies). A call with another scene or device list releases them first.
+ * with the same world (the flattened scene but its camera) on the same devices renders on them without uploading
+ * the scene, compiling or loading its kernels or allocating the level state again (another camera is handed to
+ * them first: kept_take_camera), and the one call a generated main() makes does not wait for the release (the
+ * process's exit frees the device memory, as it frees the reference's per-thread world copies). A call with another
+ * world or device list releases them first.
  */
 static struct {
     int n;
@@ -282,7 +353,7 @@ static char *
 knob_signature(void)
 {
     static const char *const per_call[] = {"FRT_DEVICES=", "FRT_GPUS=", "FRT_DEVICE=", "FRT_SEED=", "FRT_STATS_OUT=",
-                                           "FRT_RM_KEEP=", "FRT_ENCODE="};
+                                           "FRT_RM_KEEP=", "FRT_ENCODE=", "FRT_PINNED_CANVASES="};
     size_t n = 0, len = 1;
     for (char **e = environ; e != NULL && *e != NULL; ++e) {
         n += strncmp(*e, "FRT_", 4) == 0;
@@ -324,18 +395,17 @@ same_bytes(const void *a, const void *b, size_t n)
     return n == 0 || (a != NULL && b != NULL && memcmp(a, b, n) == 0);
 }
 
-/* the same flattened scene, byte for byte (padding included: a difference there only costs a fresh upload) */
+/* the same world, byte for byte (padding included: a difference there only costs a fresh upload): everything of
+ * the flattened scene that frt_scene_upload puts on the device but the camera and its sample table */
 static int
-scenes_equal(const frt_scene *a, const frt_scene *b)
+worlds_equal(const frt_scene *a, const frt_scene *b)
 {
     if (a->num_nodes != b->num_nodes || a->num_roots != b->num_roots || a->num_xforms != b->num_xforms ||
         a->prim_len != b->prim_len || a->num_materials != b->num_materials || a->num_patterns != b->num_patterns ||
         a->num_textures != b->num_textures || a->texel_len != b->texel_len || a->num_lights != b->num_lights ||
-        a->light_point_len != b->light_point_len || memcmp(&a->camera, &b->camera, sizeof(a->camera)) != 0 ||
-        memcmp(&a->config, &b->config, sizeof(a->config)) != 0) {
+        a->light_point_len != b->light_point_len || memcmp(&a->config, &b->config, sizeof(a->config)) != 0) {
         return 0;
     }
-    const size_t nst = 2 * (size_t)a->camera.usteps * (size_t)a->camera.vsteps;
     return same_bytes(a->nodes, b->nodes, sizeof(frt_node) * (size_t)a->num_nodes) &&
            same_bytes(a->roots, b->roots, sizeof(int32_t) * (size_t)a->num_roots) &&
            same_bytes(a->xforms, b->xforms, sizeof(double) * 16 * (size_t)a->num_xforms) &&
@@ -345,8 +415,29 @@ scenes_equal(const frt_scene *a, const frt_scene *b)
            same_bytes(a->textures, b->textures, sizeof(frt_texture) * (size_t)a->num_textures) &&
            same_bytes(a->texels, b->texels, sizeof(double) * (size_t)a->texel_len) &&
            same_bytes(a->lights, b->lights, sizeof(frt_light) * (size_t)a->num_lights) &&
-           same_bytes(a->light_points, b->light_points, sizeof(double) * (size_t)a->light_point_len) &&
-           same_bytes(a->sample_table, b->sample_table, sizeof(double) * nst);
+           same_bytes(a->light_points, b->light_points, sizeof(double) * (size_t)a->light_point_len);
+}
+
+/* the same camera: its bytes and its sample table's (what frt_scene_set_camera replaces on a handle) */
+static int
+cameras_equal(const frt_scene *a, const frt_scene *b)
+{
+    if (memcmp(&a->camera, &b->camera, sizeof(a->camera)) != 0) {
+        return 0;
+    }
+    const size_t nst = 2 * (size_t)a->camera.usteps * (size_t)a->camera.vsteps;
+    return same_bytes(a->sample_table, b->sample_table, sizeof(double) * nst);
+}
+
+/* Diagnostics (no device needed): how render_multi would compare two flattened scenes: bit 0 the same world (kept
+ * handles serve the call), bit 1 the same camera (they serve it as they are; else after frt_scene_set_camera) */
+int
+frt_scenes_compare(const frt_scene *a, const frt_scene *b)
+{
+    if (a == NULL || b == NULL) {
+        return 0;
+    }
+    return (worlds_equal(a, b) ? 1 : 0) | (cameras_equal(a, b) ? 2 : 0);
 }
 
 static void
@@ -363,6 +454,33 @@ release_kept(void)
     free(g_kept.knobs);
     g_kept.knobs = NULL;
     g_kept.n = 0;
+}
+
+/*
+ * The kept world under another camera: every kept handle takes fs's camera (frt_scene_set_camera) and keeps
+ * everything else, so the call uploads nothing. Returns 1, or 0 when a handle refuses the camera: the reuse has
+ * failed, and the caller releases the kept handles once and uploads afresh (the failed-reuse rule).
+ */
+static int
+kept_take_camera(const frt_scene *fs)
+{
+    const size_t nst = 2 * (size_t)fs->camera.usteps * (size_t)fs->camera.vsteps * sizeof(double);
+    double *table = (double *)malloc(nst ? nst : 1);
+    if (table == NULL || fs->sample_table == NULL) {
+        free(table);
+        return 0;
+    }
+    memcpy(table, fs->sample_table, nst);
+    for (int k = 0; k < g_kept.n; ++k) {
+        if (frt_scene_set_camera(g_kept.h[k], &fs->camera, fs->sample_table)) {
+            free(table);
+            return 0;
+        }
+    }
+    free((void *)g_kept.fs.sample_table);
+    g_kept.fs.sample_table = table;
+    g_kept.fs.camera = fs->camera;
+    return 1;
 }
 
 /*
@@ -490,7 +608,10 @@ render_multi_locked(Camera cam, World w, size_t usteps, size_t vsteps, bool jitt
     }
     char *knobs = knob_signature();
     reuse = reuse && knobs != NULL && g_kept.knobs != NULL && strcmp(knobs, g_kept.knobs) == 0 &&
-            scenes_equal(&fs, &g_kept.fs);
+            worlds_equal(&fs, &g_kept.fs);
+    if (reuse && !cameras_equal(&fs, &g_kept.fs)) {
+        reuse = kept_take_camera(&fs);
+    }
     if (!reuse) {
         release_kept();
     }
@@ -632,6 +753,152 @@ render_multi(Camera cam, World w, size_t usteps, size_t vsteps, bool jitter)
     Canvas c = render_multi_locked(cam, w, usteps, vsteps, jitter);
     pthread_mutex_unlock(&g_rm_lock);
     return c;
+}
+
+/*
+ * n cameras over one world in one strip frame on one device (the first render_multi would use): out[k] receives a
+ * fresh hsize x vsize canvas for cams[k] (canvas_alloc's ordinary memory: the caller writes and frees each), what
+ * render_multi(cams[k], w, usteps, vsteps, jitter) returns on that device, bit for bit. The cameras share their
+ * size (and, through the call, their steps and jitter). The world goes to the device as for render_multi, and its
+ * handle is kept and reused the same way (FRT_RM_KEEP). Returns 0, or -1 with the reason in frt_render_multi_error
+ * and the canvases zeroed (out[k] NULL only when out of memory).
+ */
+int
+frt_render_views(Camera *cams, size_t n, World w, size_t usteps, size_t vsteps, bool jitter, Canvas *out)
+{
+    pthread_mutex_lock(&g_rm_lock);
+    g_render_error[0] = '\0';
+    char err[512] = "";
+    int dev[FRT_MAX_RENDER_DEVICES];
+    frt_scene fs;
+    memset(&fs, 0, sizeof(fs));
+    frt_camera *fc = NULL;
+    double *buf = NULL;
+    char *knobs = NULL;
+    frt_scene_handle *h = NULL;
+    int reuse = 0, flat = 0, ok = 0;
+    size_t width = 1, height = 1;
+    if (cams == NULL || out == NULL || n == 0 || n > INT32_MAX) {
+        snprintf(err, sizeof(err), "frt_render_views: null cameras / canvases or no views");
+        out = NULL;
+        goto done;
+    }
+    for (size_t k = 0; k < n; ++k) {
+        out[k] = NULL;
+    }
+    for (size_t k = 0; k < n; ++k) {
+        if (cams[k] == NULL) {
+            snprintf(err, sizeof(err), "frt_render_views: camera %zu is null", k);
+            goto done;
+        }
+    }
+    width = cams[0]->hsize;
+    height = cams[0]->vsize;
+    for (size_t k = 0; k < n; ++k) {
+        if (cams[k]->hsize != width || cams[k]->vsize != height) {
+            snprintf(err, sizeof(err), "frt_render_views: camera %zu is %zu x %zu, camera 0 %zu x %zu: the views of a "
+                                       "strip share one size", k, cams[k]->hsize, cams[k]->vsize, width, height);
+            goto done;
+        }
+    }
+    if (render_devices(dev, FRT_MAX_RENDER_DEVICES, err, sizeof(err)) < 0) {
+        goto done;
+    }
+    if (host_flatten(cams[0], w, usteps, vsteps, jitter, &fs)) {
+        snprintf(err, sizeof(err), "%s", g_host_error);
+        goto done;
+    }
+    flat = 1;
+    fc = (frt_camera *)calloc(n, sizeof(frt_camera));
+    buf = (double *)malloc((n * width * height ? n * width * height : 1) * 4 * sizeof(double));
+    if (fc == NULL || buf == NULL) {
+        snprintf(err, sizeof(err), "out of host memory");
+        goto done;
+    }
+    for (size_t k = 0; k < n; ++k) {
+        double *table = NULL;
+        const int rc = frt_flatten_camera(cams[k], usteps, vsteps, jitter, &fc[k], &table);
+        free(table);
+        if (rc) {
+            snprintf(err, sizeof(err), "out of host memory");
+            goto done;
+        }
+    }
+    {
+        const char *keep_env = getenv("FRT_RM_KEEP");
+        const int keep = !(keep_env != NULL && atoi(keep_env) == 0);
+        knobs = knob_signature();
+        reuse = keep && g_kept.n == 1 && g_kept.dev[0] == dev[0] && g_kept.h[0] != NULL && knobs != NULL &&
+                g_kept.knobs != NULL && strcmp(knobs, g_kept.knobs) == 0 && worlds_equal(&fs, &g_kept.fs);
+        if (reuse && !cameras_equal(&fs, &g_kept.fs)) {
+            reuse = kept_take_camera(&fs);
+        }
+        if (reuse) {
+            h = g_kept.h[0];
+        } else {
+            release_kept();
+            if (frt_scene_upload(&fs, dev[0], &h)) {
+                snprintf(err, sizeof(err), "device %d: upload: %s", dev[0], frt_last_error());
+                h = NULL;
+                goto done;
+            }
+        }
+        const char *seed_env = getenv("FRT_SEED");
+        frt_frame_params p;
+        memset(&p, 0, sizeof(p));
+        p.row_end = (int64_t)height;
+        p.row_stride = 1;
+        p.seed = seed_env ? strtoull(seed_env, NULL, 10) : 0x5eedULL;
+        if (frt_render_views_host(h, fc, (int32_t)n, &p, buf, NULL)) {
+            snprintf(err, sizeof(err), "device %d: render: %s", dev[0], frt_last_error());
+        } else {
+            ok = 1;
+            frt_encode_note_device(dev[0]);
+        }
+        if (reuse) {
+            if (!ok) {
+                release_kept();  /* (a failed call keeps nothing) */
+            }
+        } else if (ok && keep) {
+            g_kept.n = 1;
+            g_kept.dev[0] = dev[0];
+            g_kept.h[0] = h;
+            g_kept.fs = fs;
+            flat = 0;
+            g_kept.knobs = knobs;
+            knobs = NULL;
+        } else {
+            frt_scene_release(h);
+        }
+    }
+done:
+    for (size_t k = 0; out != NULL && k < n; ++k) {
+        out[k] = canvas_alloc(width, height, false, NULL);
+        if (out[k] == NULL || out[k]->arr == NULL) {
+            if (ok) {
+                snprintf(err, sizeof(err), "out of host memory");
+            }
+            ok = 0;
+            continue;
+        }
+        if (ok) {
+            memcpy(out[k]->arr, buf + k * width * height * 4, width * height * sizeof(Color));
+        } else {
+            memset(out[k]->arr, 0, width * height * sizeof(Color));
+        }
+    }
+    if (!ok) {
+        fprintf(stderr, "frt: frt_render_views failed: %s\n", err);
+        snprintf(g_render_error, sizeof(g_render_error), "%s", err[0] ? err : "failed");
+    }
+    if (flat) {
+        frt_flat_scene_free(&fs);
+    }
+    free(knobs);
+    free(fc);
+    free(buf);
+    pthread_mutex_unlock(&g_rm_lock);
+    return ok ? 0 : -1;
 }
 
 Canvas

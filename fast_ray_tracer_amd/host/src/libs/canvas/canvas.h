@@ -31,9 +31,11 @@ void ppm_free(Ppm p);
 
 /* (frt: render_multi's canvas, its array in page-locked memory that the device writes by DMA; canvas_free hands the
  * array to a one-entry pool the next such canvas of the same size reuses. frt_canvas_pool_release frees the pooled
- * array: frt_render_multi_release calls it) */
+ * array: frt_render_multi_release calls it. At most FRT_PINNED_CANVASES, default 4, such arrays are out at once; a
+ * canvas asked for beyond that gets canvas_alloc's ordinary memory, and frt_canvas_is_pinned tells which it got) */
 Canvas frt_canvas_alloc_pinned(size_t width, size_t height, bool super_sample, void (*color_space_fn)(const Color, Color));
 void frt_canvas_pool_release(void);
+int frt_canvas_is_pinned(Canvas c);
 
 /* (frt: the 16-bit values of write_ppm_file / write_png come from the host pass or, byte-identical, from the device:
  * FRT_ENCODE=host | device | auto, default auto = the device once this process has rendered on one.

@@ -31,4 +31,16 @@ Canvas render_multi(Camera cam, World w, size_t usteps, size_t vsteps, bool jitt
 const char *frt_render_multi_error(void);
 void frt_render_multi_release(void);
 
+/* A camera at `from` looking at `to` (view_transform, then camera(): the order a generated main() uses) with the
+ * aperture and steps of `like`; released with free(), and not to outlive `like` (it shares the aperture's sampler
+ * tables). A main() that loops over such cameras and calls render_multi for each keeps its world on the device:
+ * only the first call uploads (host/frt_render.c, INTEGRATION.md "Views"). */
+/* n cameras of one size over one world as one strip frame on one device: out[k] receives a fresh canvas for cams[k]
+ * (the caller frees each), what render_multi(cams[k], w, usteps, vsteps, jitter) returns on that device, bit for
+ * bit. Returns 0, or -1 with the reason in frt_render_multi_error and the canvases zeroed (host/frt_render.c). */
+int frt_render_views(Camera *cams, size_t n, World w, size_t usteps, size_t vsteps, bool jitter, Canvas *out);
+
+Camera frt_camera_look_at(const double from[3], const double to[3], const double up[3], size_t hsize, size_t vsize,
+                          double fov, double distance, Camera like);
+
 #endif

@@ -124,6 +124,18 @@ def host_lib(auto_build: bool = False) -> ctypes.CDLL:
         lib.frt_host_prepare.restype = vp
         lib.frt_host_prepare.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_bool, ctypes.c_int]
         lib.frt_host_last_error.restype = ctypes.c_char_p
+        lib.frt_host_set_camera.restype = ctypes.c_int
+        lib.frt_host_set_camera.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_bool]
+        lib.frt_camera_look_at.restype = vp
+        lib.frt_camera_look_at.argtypes = [ctypes.POINTER(ctypes.c_double)] * 3 + [
+            ctypes.c_size_t, ctypes.c_size_t, ctypes.c_double, ctypes.c_double, vp]
+        for fn in ("frt_camera_fov", "frt_camera_distance", "frt_camera_aperture_size"):
+            getattr(lib, fn).restype = ctypes.c_double
+            getattr(lib, fn).argtypes = [vp]
+        lib.frt_camera_set_aperture_size.restype = None
+        lib.frt_camera_set_aperture_size.argtypes = [vp, ctypes.c_double]
+        lib.frt_camera_free.restype = None
+        lib.frt_camera_free.argtypes = [vp]
         lib.frt_device_count.restype = ctypes.c_int
         lib.frt_last_error.restype = ctypes.c_char_p
         lib.frt_render_rows.restype = ctypes.c_int
@@ -196,6 +208,61 @@ class Scene:
     def spp(self) -> int:
         return self.usteps * self.vsteps
 
+    def view(self, from_, to, up=(0.0, 1.0, 0.0), hsize: int | None = None, vsize: int | None = None,
+             fov: float | None = None, distance: float | None = None, aperture_size: float | None = None,
+             usteps: int | None = None, vsteps: int | None = None, name: str | None = None) -> "View":
+        """This scene's world seen from `from_` towards `to`: a camera built by the host library as a generated
+        main() builds its own (frt_camera_look_at: view_transform, then camera()), with this scene's aperture,
+        steps and jitter; size, field of view, canvas distance, aperture size and the render call's steps default to
+        the captured ones."""
+        lib = host_lib()
+        v3 = ctypes.c_double * 3
+        cam = lib.frt_camera_look_at(v3(*from_), v3(*to), v3(*up),
+                                     self.width if hsize is None else hsize, self.height if vsize is None else vsize,
+                                     lib.frt_camera_fov(self.camera) if fov is None else fov,
+                                     lib.frt_camera_distance(self.camera) if distance is None else distance,
+                                     self.camera)
+        if not cam:
+            raise RuntimeError("frt: frt_camera_look_at failed")
+        if aperture_size is not None:
+            lib.frt_camera_set_aperture_size(cam, aperture_size)
+        v = View(self, cam, self.usteps if usteps is None else usteps, self.vsteps if vsteps is None else vsteps,
+                 self.jitter, self.drand48_state,
+                 name or "%s@%s" % (self.name, ",".join("%g" % x for x in from_)))
+        weakref.finalize(v, lib.frt_camera_free, cam)
+        return v
+
+    def view_of(self, other: "Scene") -> "View":
+        """This scene's world under another capture's camera, steps, jitter and drand48 state (a golden that
+        differs from this one only in its camera(...) / aperture(...) lines)."""
+        return View(self, other.camera, other.usteps, other.vsteps, other.jitter, other.drand48_state,
+                    "%s@%s" % (self.name, other.name), keep=other)
+
+
+class View:
+    """A camera over a captured Scene's world. It carries the attributes a Scene has (camera, world, usteps, vsteps,
+    jitter, width, height, drand48_state, name), so whatever renders a Scene renders a View: render_multi(view),
+    the oracle, GpuRenderer.set_camera(view) / render_views([...])."""
+
+    def __init__(self, base: Scene, camera, usteps: int, vsteps: int, jitter: bool, drand48_state, name: str,
+                 keep=None):
+        lib = host_lib()
+        self.base = base.base if isinstance(base, View) else base  # (keeps the world, and the aperture's tables, alive)
+        self._keep = keep
+        self.camera = camera
+        self.world = base.world
+        self.usteps = int(usteps)
+        self.vsteps = int(vsteps)
+        self.jitter = bool(jitter)
+        self.drand48_state = tuple(drand48_state)
+        self.width = int(lib.frt_camera_hsize(camera))
+        self.height = int(lib.frt_camera_vsize(camera))
+        self.name = name
+
+    @property
+    def spp(self) -> int:
+        return self.usteps * self.vsteps
+
 
 class GpuRenderer:
     """render_multi's device path for one captured scene on one HIP device."""
@@ -207,11 +274,74 @@ class GpuRenderer:
         # the handles an earlier render_multi kept hold their device memory until released (GBs for a GI scene)
         release_render_multi()
         self.scene = scene
+        self.frame = scene  # (whose camera the handle holds: the scene, or set_camera's view)
         self.device = device
         h = self.lib.frt_host_prepare(scene.camera, scene.world, scene.usteps, scene.vsteps, scene.jitter, device)
         if not h:
             raise RuntimeError("frt: scene upload failed: " + self.lib.frt_host_last_error().decode())
         self.handle = h
+
+    def set_camera(self, view) -> None:
+        """Move the resident scene's camera to `view` (a View of this scene's world, or the Scene itself to go
+        back): frt_host_set_camera. Only the camera (and, for other steps, the sample table) goes to the device;
+        the world, its kernels, the level state and a GI scene's photon maps stay. Later render / render_into /
+        render_encoded calls produce view.height x view.width frames. On a refusal it raises, and the renderer
+        keeps the camera it had."""
+        if view.world != self.scene.world:
+            raise ValueError("frt: set_camera needs a view of this renderer's world (Scene.view / Scene.view_of)")
+        if self.lib.frt_host_set_camera(self.handle, view.camera, view.usteps, view.vsteps, view.jitter) != 0:
+            raise RuntimeError("frt: set_camera failed: " + self.lib.frt_host_last_error().decode())
+        self.frame = view
+
+    def render_views(self, views, row_begin: int = 0, row_end: int | None = None, row_stride: int = 1,
+                     seed: int = 0x5EED, batch_samples: int = 0, stats: bool = False, precision: str | None = None):
+        """Render K views of this renderer's world in one frame, a strip (frt_render_views_host): an array
+        (K, rows, width, 4) float64 in ordinary pageable memory, view k bit for bit what set_camera(views[k])
+        followed by render(...) with the same arguments gives. The views share their size, steps and jitter; the row
+        range and stride apply inside each view. The levels' launches and count read-backs are paid once for the
+        strip, not once per view. The renderer's own camera is unchanged afterwards."""
+        views = list(views)
+        if not views:
+            raise ValueError("frt: render_views needs at least one view")
+        if any(v.world != self.scene.world for v in views):
+            raise ValueError("frt: render_views needs views of this renderer's world (Scene.view / Scene.view_of)")
+        lib = self.lib
+        lib.frt_camera_size.restype = ctypes.c_size_t
+        lib.frt_flatten_camera.restype = ctypes.c_int
+        lib.frt_flatten_camera.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_bool,
+                                           ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
+        lib.frt_render_views_host.restype = ctypes.c_int
+        lib.frt_render_views_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                              ctypes.POINTER(FrameParams), ctypes.c_void_p, ctypes.POINTER(FrameStats)]
+        size = lib.frt_camera_size()
+        cams = ctypes.create_string_buffer(size * len(views))
+        for k, v in enumerate(views):
+            table = ctypes.c_void_p()
+            rc = lib.frt_flatten_camera(v.camera, v.usteps, v.vsteps, v.jitter, ctypes.addressof(cams) + k * size,
+                                        ctypes.byref(table))
+            lib.frt_camera_free(table)  # (free(): the strip uses the handle's table)
+            if rc:
+                raise RuntimeError("frt: out of host memory for a view's sample table")
+        first, own = views[0], self.frame
+        # the handle's sample table is the strip's: a strip of other steps borrows the handle for its first view
+        borrow = (first.usteps, first.vsteps) != (own.usteps, own.vsteps)
+        if borrow:
+            self.set_camera(first)
+        try:
+            p = self._params(row_begin, first.height if row_end is None else row_end, row_stride, seed, batch_samples,
+                             precision)
+            n = self.rows_in(p.row_begin, p.row_end, row_stride)
+            out = np.zeros((len(views), n, first.width, 4), dtype=np.float64)
+            st = FrameStats()
+            rc = lib.frt_render_views_host(self.handle, cams, len(views), ctypes.byref(p),
+                                           out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(st) if stats else None)
+            err = lib.frt_last_error().decode() if rc != 0 else ""
+        finally:
+            if borrow:
+                self.set_camera(own)
+        if rc != 0:
+            raise RuntimeError("frt render_views failed: " + err)
+        return (out, st) if stats else out
 
     def close(self) -> None:
         if getattr(self, "handle", None):
@@ -231,7 +361,7 @@ class GpuRenderer:
             raise ValueError("frt: precision %r is not supported (\"parity\", \"fast32\" or None)" % (precision,))
         p.precision = precision if isinstance(precision, int) else PRECISION[precision]
         p.row_begin = row_begin
-        p.row_end = self.scene.height if row_end is None else row_end
+        p.row_end = self.frame.height if row_end is None else row_end
         p.row_stride = row_stride
         p.seed = seed
         p.batch_samples = batch_samples
@@ -247,7 +377,7 @@ class GpuRenderer:
         default), "fast32" (the light-point loop in binary32) or None (FRT_PRECISION decides, else parity)."""
         p = self._params(row_begin, row_end, row_stride, seed, batch_samples, precision)
         n = self.rows_in(p.row_begin, p.row_end, row_stride)
-        out = np.zeros((n, self.scene.width, 4), dtype=np.float64)
+        out = np.zeros((n, self.frame.width, 4), dtype=np.float64)
         st = FrameStats()
         rc = self.lib.frt_render_rows(self.handle, ctypes.byref(p), out.ctypes.data_as(ctypes.c_void_p),
                                       ctypes.byref(st) if stats else None)
@@ -273,9 +403,9 @@ class GpuRenderer:
         stats dict); render_args as render_into's (seed, batch_samples, precision)."""
         import torch
         with torch.cuda.device(self.device):
-            frame = torch.empty((self.scene.height, self.scene.width, 4), dtype=torch.float64, device="cuda")
+            frame = torch.empty((self.frame.height, self.frame.width, 4), dtype=torch.float64, device="cuda")
         self.render_into(frame.data_ptr(), **render_args)
-        return _encode16(frame.data_ptr(), True, self.scene.width, self.scene.height, mode, "device", self.device)
+        return _encode16(frame.data_ptr(), True, self.frame.width, self.frame.height, mode, "device", self.device)
 
 
 def render_multi(scene: Scene, devices: str | None = None) -> np.ndarray:
@@ -283,7 +413,12 @@ def render_multi(scene: Scene, devices: str | None = None) -> np.ndarray:
     (host/frt_render.c; reference renderer.c:244) on the captured scene — flatten, upload
     (incl. the scene-specialised kernel's compile), render over the selected devices
     (``FRT_DEVICES`` list, e.g. "0,0"; default every visible GPU), copy to the host canvas.
-    Returns the (height, width, 4) canvas; render_multi's failures are logged by it and
+    A call whose world, config, knobs and devices equal the previous call's and whose camera alone differs (a
+    View of the same Scene) moves the camera of the handles it kept and uploads nothing.
+    Returns the (height, width, 4) canvas. The array is the canvas's own memory, not a copy: for up to
+    FRT_PINNED_CANVASES (default 4) canvases alive at once it aliases page-locked (hipHostMalloc) memory, which goes
+    back to the library's pool when the array is collected; canvases kept beyond that number are ordinary malloc'd
+    memory. Copy an array you mean to keep for long (np.array(c)). render_multi's failures are logged by it and
     leave the canvas zeroed (the reference has no error return); ``frt_render_multi_error``
     (host/frt_render.c) names the failure, and it raises here."""
     lib = host_lib()

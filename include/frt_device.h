@@ -280,6 +280,18 @@ const char *frt_last_error(void);
 /* copy a flattened scene into HBM on `device`; the host scene may be freed afterwards */
 int frt_scene_upload(const frt_scene *scene, int device, frt_scene_handle **out);
 
+/*
+ * Replace the handle's camera; later frames render cam's hsize x vsize. Nothing on the device but the camera depends
+ * on it (it enters through camera_ray alone, csrc/frt_camera.hpp), so the scene buffers, the loaded kernels, the
+ * level state (which grows on demand, as ever) and the photon maps stay: with global illumination a frame after
+ * this call with an unchanged seed reports photon_pass == 0. sample_table holds 2 * usteps * vsteps doubles, as
+ * frt_scene.sample_table does, and is uploaded again only when its size or contents differ from the handle's.
+ * Returns 0, or -1 with the reason in frt_last_error for a null pointer, a size or step count <= 0, more than
+ * 2^31 - 1 samples per pixel or more than 2^52 samples per frame (the engine's 32-bit sample-in-pixel and 64-bit
+ * path-node key); after a failure the handle keeps its old camera and stays usable.
+ */
+int frt_scene_set_camera(frt_scene_handle *h, const frt_camera *cam, const double *sample_table);
+
 /* render rows into a host buffer (rows x hsize x 4 doubles, rows in the order rendered) */
 int frt_render_rows(frt_scene_handle *h, const frt_frame_params *params, double *host_rgba,
                     frt_frame_stats *stats);
@@ -287,6 +299,20 @@ int frt_render_rows(frt_scene_handle *h, const frt_frame_params *params, double 
 /* same, writing into device memory on the handle's device (e.g. a torch tensor's storage) */
 int frt_render_rows_device(frt_scene_handle *h, const frt_frame_params *params, double *device_rgba,
                            frt_frame_stats *stats);
+
+/*
+ * Render nviews cameras over the handle's scene in one frame: a strip. The views share hsize, vsize, usteps, vsteps
+ * and jitter (and the steps are the handle's own, whose sample table they use: frt_scene_set_camera one of them
+ * first otherwise); they may differ in transform, field-of-view scalars and aperture. Anything else is refused with
+ * the reason in frt_last_error. params' row range and stride apply inside each view, and the output is view-major:
+ * nviews x rows x hsize x 4 doubles. View k is, bit for bit, what frt_scene_set_camera(cams[k]) followed by
+ * frt_render_rows* with the same params (seed included) renders; the levels' launches and count read-backs are
+ * paid once for the strip instead of once per view. The handle's own camera is unchanged afterwards.
+ */
+int frt_render_views_host(frt_scene_handle *h, const frt_camera *cams, int32_t nviews, const frt_frame_params *params,
+                          double *host_rgba, frt_frame_stats *stats);
+int frt_render_views_device(frt_scene_handle *h, const frt_camera *cams, int32_t nviews,
+                            const frt_frame_params *params, double *device_rgba, frt_frame_stats *stats);
 
 void frt_scene_release(frt_scene_handle *h);
 
