@@ -124,27 +124,47 @@ __device__ __forceinline__ void ray_for_pixel(const frt_camera& cam, double px, 
     normalize3(v, r.d);
 }
 
+// global sample index of sample s of a batch's level 0: the pixel's index in the whole frame (the batch's rows may be
+// a strided part of it) times spp plus the sub-pixel sample (sub = v * usteps + u). The one place the expression
+// lives: camera_ray and camera_key (the level-0 keys that HeadCols does not store) both take it from here.
+struct CameraSample {
+    int64_t row, col;
+    uint64_t global_pixel, global_sample;
+    int sub;
+};
+__device__ __forceinline__ CameraSample camera_sample(const DevScene& S, const Batch& B, int64_t s) {
+    CameraSample c;
+    const int64_t pix = B.pixel_begin + s / B.spp;
+    c.sub = (int)(s % B.spp);
+    const int64_t hs = S.cam.hsize;
+    c.row = B.row_begin + (pix / hs) * B.row_stride;
+    c.col = pix % hs;
+    c.global_pixel = (uint64_t)(c.row * hs + c.col);
+    c.global_sample = c.global_pixel * (uint64_t)B.spp + (uint64_t)c.sub;
+    return c;
+}
+
+// a level-0 path node's key: (global sample << 12) | heap code 1 (the root of the sample's path tree)
+__device__ __forceinline__ uint64_t camera_key(const DevScene& S, const Batch& B, int64_t s) {
+    return (camera_sample(S, B, s).global_sample << 12) | 1ull;
+}
+
 // camera ray of sample s of a batch (k_trace level 0 and k_prepare level 0)
 __device__ __forceinline__ void camera_ray(const DevScene& S, const Batch& B, int64_t s, Ray& r, uint64_t& key,
                                            unsigned& err) {
-    const int64_t pix = B.pixel_begin + s / B.spp;
-    const int sub = (int)(s % B.spp);  // sub = v * usteps + u
-    const int64_t hs = S.cam.hsize;
-    const int64_t row = B.row_begin + (pix / hs) * B.row_stride;
-    const int64_t col = pix % hs;
-    const uint64_t global_pixel = (uint64_t)(row * hs + col);
-    const uint64_t global_sample = global_pixel * (uint64_t)B.spp + (uint64_t)sub;
+    const CameraSample c = camera_sample(S, B, s);
+    const int sub = c.sub;
     double jit[2], ap[2] = {0.5, 0.5};
     if (S.cam.jitter) {
         const int U = (int)S.cam.usteps, V = (int)S.cam.vsteps;
-        cmj_point(B.seed, global_pixel, U, V, sub % U, sub / U, jit);
+        cmj_point(B.seed, c.global_pixel, U, V, sub % U, sub / U, jit);
     } else {
         jit[0] = S.sample_table[2 * sub];
         jit[1] = S.sample_table[2 * sub + 1];
     }
-    if (S.cam.aperture_size != 0.0) aperture_point(S.cam, B.seed, global_sample, ap, err);
-    ray_for_pixel(S.cam, (double)col, (double)row, jit, ap, r);
-    key = (global_sample << 12) | 1ull;
+    if (S.cam.aperture_size != 0.0) aperture_point(S.cam, B.seed, c.global_sample, ap, err);
+    ray_for_pixel(S.cam, (double)c.col, (double)c.row, jit, ap, r);
+    key = (c.global_sample << 12) | 1ull;
 }
 
 }  // namespace frt

@@ -72,7 +72,7 @@ struct NodeRec {
 static_assert(sizeof(NodeRec) == 216, "NodeRec layout");
 
 // NodeRec in HBM: the fields every path node needs (10 column words), its over_point and key from the
-// node's ShadowHead (which k_prepare writes for the shadow pass anyway: no second copy), and its material
+// level's HeadCols (which k_prepare writes for the shadow pass anyway: no second copy), and its material
 // colours (13 words), which k_prepare stores only for materials with patterns on them (kOwnColors; every
 // other reader takes them from the material table): the colours of pattern-free materials are never
 // written or read per node, and a missed ray writes only its material / parent / slot words. Words that a
@@ -96,7 +96,7 @@ enum : int32_t { kOwnColors = 64, kOwnD = 128 };  // (NodeFlags bits) the node's
 struct NodeCols {
     Cols<NodeCore> core;
     Cols<NodeColors> col;
-    const ShadowHead* head = nullptr;  // over_point, key (the level's ShadowHead array)
+    HeadCols head;                     // over_point, key (the level's shadow-pass columns; head.mat is core word 0)
     int32_t root = 0;                  // level 0: parent / slot are -1 / 0 and not stored
     // level 0 of a scene without GI: eyev is the camera ray's direction negated, which its one reader (shade_node,
     // through camera_eyev) recomputes from the node's sample; its 24 bytes per node are not stored
@@ -168,13 +168,12 @@ struct NodeCols {
         NodeCore c;
         __builtin_memcpy(&c, t, sizeof(c));
         NodeRec v;
-        const ShadowHead& hd = head[i];  // (dead, and not loaded, where a kernel uses neither field)
+        head.over_point(i, v.over_point);  // (dead, and not loaded, where a kernel does not use it)
         for (int k = 0; k < 3; ++k) {
-            v.over_point[k] = hd.over_point[k];
             v.normalv[k] = c.normalv[k];
             v.eyev[k] = c.eyev[k];
         }
-        v.key = hd.key;
+        v.key = head.key != nullptr ? head.key[i] : 0ull;  // (a level without stored keys: key(), for the kernels that use it)
         v.material = c.material;
         v.parent = c.parent;
         v.slot = c.slot;
@@ -204,6 +203,10 @@ struct NodeCols {
             v.Ns = M.Ns;
         }
         return v;
+    }
+    // node i's key: stored, or derived where the level stores none (head_key)
+    __device__ __forceinline__ uint64_t key(const DevScene& S, const Batch& B, int64_t i) const {
+        return head_key(S, B, head, i);
     }
 };
 
@@ -304,8 +307,7 @@ __global__ void __launch_bounds__(kTraceBlock) k_trace_redo(DevScene S, Batch B,
 template <bool kPat>
 __device__ __forceinline__ bool prepare_node(const DevScene& S, const Batch& B, const QueuedRay* __restrict__ q,
                                              int64_t n, const HitRec* __restrict__ hits, const double* __restrict__ hn12,
-                                             NodeCols& rec,
-                                             ShadowHead* __restrict__ heads, QueuedRay* __restrict__ next_q,
+                                             NodeCols& rec, QueuedRay* __restrict__ next_q,
                                              unsigned long long* counters, unsigned* err, int64_t node, double* op,
                                              int* spawned, int uniform_ok) {
     // this block's counter line: next-level queue segment count (word level + 1), pruned (16), hits (17), waves
@@ -343,8 +345,7 @@ __device__ __forceinline__ bool prepare_node(const DevScene& S, const Batch& B, 
     const HitRec hr = hits[node];
     PSTAMP(1);
     if (hr.node < 0) {
-        rec.store_miss(node, parent, slot);
-        heads[node].material = -1;
+        rec.store_miss(node, parent, slot);  // (material -1: what the shadow pass tests too, HeadCols::hit)
         return false;
     }
     // the rest per hit: on the scene as it is (leaf: the lane's own), or on its uniform view where every lane of the
@@ -457,25 +458,10 @@ __device__ __forceinline__ bool prepare_node(const DevScene& S, const Batch& B, 
     // the colours per node only where a pattern makes them vary (prepare: map_Ka / Kd / Ks / refl / Ns)
     const bool own = kPat && (M.map_Ka >= 0 || M.map_Kd >= 0 || M.map_Ks >= 0 || M.map_refl >= 0 || M.map_Ns >= 0);
     rec.store(node, nr, own, kPat && M.map_d >= 0);
-    ShadowHead hd;
-    for (int k = 0; k < 3; ++k) hd.over_point[k] = c.over_point[k];
-    hd.key = key;
-    hd.material = c.material;
-    hd.pad = 0;
-#ifdef FRT_EXPERIMENT_HEAD_COLS
-    // (measurements only — wrong images: the head's five words stored as five columns of the same 40n bytes, word f
-    // of node i at word f * n + i, which nobody reads back as such: what k_prepare's time would be with a columnar
-    // ShadowHead, before any reader is changed; profiles/r07_ab_head_cols.txt)
-    {
-        uint64_t t[5];
-        __builtin_memcpy(t, &hd, sizeof(hd));
-        uint64_t* w = (uint64_t*)heads;
+    // the shadow pass's columns: three coalesced 8-byte stores, and the key where the level stores its keys
 #pragma unroll
-        for (int f = 0; f < 5; ++f) w[(int64_t)f * n + node] = t[f];
-    }
-#else
-    heads[node] = hd;
-#endif
+    for (int k = 0; k < 3; ++k) rec.head.op[k * rec.head.cap + node] = c.over_point[k];
+    if (rec.head.key != nullptr) rec.head.key[node] = key;
     PSTAMP(4);
     for (int k = 0; k < 3; ++k) op[k] = c.over_point[k];
     };
@@ -534,7 +520,7 @@ template <bool kPat>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kPat ? 1 : FRT_PREPARE_WAVES, 8)))
 k_prepare(DevScene S, Batch B, const QueuedRay* __restrict__ q, int64_t n, const HitRec* __restrict__ hits,
           const double* __restrict__ hn12,
-          NodeCols rec, ShadowHead* __restrict__ heads, QueuedRay* __restrict__ next_q, unsigned long long* counters,
+          NodeCols rec, QueuedRay* __restrict__ next_q, unsigned long long* counters,
           unsigned* err, float* __restrict__ tbox, int tile_log2, float* __restrict__ stbox, int sub_log2,
           int32_t* __restrict__ counts, unsigned long long* __restrict__ spawn_masks, int uniform_ok) {
     const int64_t node = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -548,7 +534,7 @@ k_prepare(DevScene S, Batch B, const QueuedRay* __restrict__ q, int64_t n, const
     // reflected / refracted bits as masks g / G + g, G = the level's waves; every wave writes both, no clearing)
     int spawned = 0;
     if (node < n)
-        hit = prepare_node<kPat>(S, B, q, n, hits, hn12, rec, heads, next_q, counters, err, node, op,
+        hit = prepare_node<kPat>(S, B, q, n, hits, hn12, rec, next_q, counters, err, node, op,
                                  spawn_masks != nullptr ? &spawned : nullptr, uniform_ok);
     if (spawn_masks != nullptr) {  // (every lane of the wave is here)
         const unsigned long long mr = __ballot(spawned & 1), mt = __ballot((spawned >> 1) & 1);
@@ -568,7 +554,7 @@ k_prepare(DevScene S, Batch B, const QueuedRay* __restrict__ q, int64_t n, const
 #define FRT_SHADOW_ATTR
 #endif
 template <int kFeat>
-__global__ void __launch_bounds__(kTraceBlock) FRT_SHADOW_ATTR k_shadow(DevScene S, Batch B, const ShadowHead* __restrict__ shead, int64_t n,
+__global__ void __launch_bounds__(kTraceBlock) FRT_SHADOW_ATTR k_shadow(DevScene S, Batch B, const HeadCols shead, int64_t n,
                                                         const int32_t* __restrict__ j_light,
                                                         const int32_t* __restrict__ j_point, int32_t samples_per_node,
                                                         int32_t* __restrict__ counts, unsigned* err) {
@@ -590,7 +576,7 @@ __global__ void __launch_bounds__(kTraceBlock) FRT_SHADOW_ATTR k_shadow(DevScene
 // with non-finite components, which its decisions do not cover — through the
 // generic walk; grid-stride over the queue, whole waves per step, one atomic per lit lane
 template <int kFeat>
-__global__ void __launch_bounds__(kTraceBlock) k_shadow_redo(DevScene S, Batch B, const ShadowHead* __restrict__ shead, int64_t n,
+__global__ void __launch_bounds__(kTraceBlock) k_shadow_redo(DevScene S, Batch B, const HeadCols shead, int64_t n,
                                                              const int32_t* __restrict__ j_light,
                                                              const int32_t* __restrict__ j_point, int32_t samples_per_node,
                                                              int32_t* __restrict__ counts, unsigned* err,
@@ -1151,6 +1137,7 @@ __global__ void __launch_bounds__(kBlock) k_shade(DevScene S, Batch B, NodeCols 
     NodeRec nr{};
     if (i < n) {
         nr = rec.load(i, S.materials);
+        if (!kLazy) nr.key = rec.key(S, B, i);
         mine = nr.material >= 0;
         heavy = mine && lit != nullptr && shade_heavy(S, counts, i);
     }
@@ -1231,7 +1218,7 @@ __device__ __forceinline__ unsigned lit_total(const unsigned* __restrict__ lcoun
 }
 
 // the listed nodes densely with their rows of light sort_light (the sort's keys and values)
-__global__ void __launch_bounds__(kBlock) k_lit_rows(DevScene S, Batch B, const ShadowHead* __restrict__ head,
+__global__ void __launch_bounds__(kBlock) k_lit_rows(DevScene S, Batch B, const HeadCols head,
                                                      const uint32_t* __restrict__ lit, const unsigned* __restrict__ lcount,
                                                      uint32_t segcap, int sort_light, uint32_t* __restrict__ rows,
                                                      uint32_t* __restrict__ nodes) {
@@ -1241,12 +1228,12 @@ __global__ void __launch_bounds__(kBlock) k_lit_rows(DevScene S, Batch B, const 
     const size_t slot = jit::mix_slot(m < total ? m : 0u, lcount, segcap);
     if (m >= total) return;
     const uint32_t i = lit[slot];
-    rows[m] = (uint32_t)light_row(S.lights[sort_light], B.seed, head[i].key, sort_light, 1);
+    rows[m] = (uint32_t)light_row(S.lights[sort_light], B.seed, head_key(S, B, head, i), sort_light, 1);
     nodes[m] = i;
 }
 
 // The multi-row light's shading in row order without scattered record traffic (FRT_SHADE_STAGE=1; scenes without
-// GI; the default, 2, keeps only the triples' part): in row order every lane's node is a random one, so its ~10 record words (NodeCols columns, ShadowHead,
+// GI; the default, 2, keeps only the triples' part): in row order every lane's node is a random one, so its ~10 record words (NodeCols columns, HeadCols,
 // counts) were ~10 scattered lines per node and its 9 colour-column stores 9 partial lines (profiles/
 // r05_pmc_k_shade_lit_shipped.json: 7.5 GB fetched, 5.1 GB written per launch for 0.8 GB of triples). k_lit_stage
 // reads the records in list order (the list is in node order within each wave: near-coalesced) and writes what the
@@ -1274,6 +1261,7 @@ __global__ void __launch_bounds__(kBlock) k_lit_stage(DevScene S, Batch B, NodeC
     if (m >= total) return;
     const uint32_t i = lit[slot];
     NodeRec nr = rec.load(i, S.materials);
+    nr.key = rec.key(S, B, i);
     if (rec.eye_cam) camera_eyev(S, B, i, nr.eyev);
     LitStage r;
     for (int k = 0; k < 3; ++k) {
@@ -1356,6 +1344,7 @@ __device__ __forceinline__ void shade_lit_body(const DevScene& S, const Batch& B
             i = (int64_t)lit[slot];
         }
         nr = rec.load(i, S.materials);
+        nr.key = rec.key(S, B, i);
         if (rec.eye_cam) camera_eyev(S, B, i, nr.eyev);
     }
     if (staged) {  // (the colours: a pattern node's own, or its material's)
@@ -2304,7 +2293,7 @@ struct frt_scene_handle {
     frt_frame_stats* cur_st = nullptr;  // the instrumented frame's stats (sub-kernel timers), else null
     uint64_t rays_walked = 0;           // shadow rays walked one by one in this frame
     uint64_t pairs_walked = 0;          // (node, light part) pairs they belong to (list entries walked)
-    uint64_t heads_walked = 0;          // ShadowHeads the per-ray kernel read (a node per lane group of an entry)
+    uint64_t heads_walked = 0;          // nodes whose head words the per-ray kernel read (a node per lane group of an entry)
     unsigned long long uniform_stats[3] = {0, 0, 0};  // FRT_JIT_STATS: (node, light) pairs all lit / all shadowed / mixed
     // k_shade's list of nodes with light-point work (kShadeSegs segments) and its segment counters
     uint32_t* shade_lit = nullptr;
@@ -2341,7 +2330,8 @@ struct frt_scene_handle {
     // work buffers (grow on demand)
     struct Level {
         frt::NodeCols rec;
-        frt::ShadowHead* head = nullptr;
+        double* head_op = nullptr;     // the shadow pass's over_point columns, 24 bytes per node (rec.head, HeadCols)
+        uint64_t* head_key = nullptr;  // its key column, 8 bytes per node, where the level stores keys (level_keyed)
         frt::QueuedRay* q = nullptr;
         frt::Cols<frt::Tri9> surface;
         frt::Cols<frt::Tri9> child;  // two slots per node: i (reflected), cap + i (refracted), cap = the level's
@@ -3745,7 +3735,8 @@ void frt_scene_release(frt_scene_handle* h) {
     for (void* p : h->owned) hip_ignore(hipFree(p));
     for (auto& L : h->levels) {
         hip_ignore(hipFree(L.rec.core.w));
-        hip_ignore(hipFree(L.head));
+        hip_ignore(hipFree(L.head_op));
+        hip_ignore(hipFree(L.head_key));
         hip_ignore(hipFree(L.q));
         hip_ignore(hipFree(L.surface.w));
         hip_ignore(hipFree(L.child.w));
@@ -3811,13 +3802,44 @@ static int32_t level_eye_cam(const frt_scene_handle* h, size_t d) {
     return d == 0 && !h->S.cfg.use_gi && eye_cam_env && h->strip_views == 0 ? 1 : 0;
 }
 
+// A level stores its nodes' keys unless they are camera_ray's own, which the readers derive (head_key, camera_key):
+// level 0 of a frame of the handle's camera. Level 0 of a strip of views takes its rays, keys included, from
+// k_view_rays' queue; with GI the gather kernels read a node's key without the batch it belongs to; and with a
+// multi-row light, whose row the key picks in every lane of the per-ray shadow kernel, the stored key is an 8-byte
+// load where the derived one is two 64-bit divisions per lane (shipped frame 56.4 -> 59.3 ms with the derived key,
+// profiles/r08_ab_head_cols.txt; FRT_HEAD_KEY0=0, read per frame: level 0 derives them there too, A/B runs and
+// tests/test_head_cols.py). What is left deriving is nobody's hot path: a single-row light's row is 0.
+static bool level_keyed(const frt_scene_handle* h, size_t d) {
+    bool multi = false;
+    for (const auto& L : h->host_lights) multi = multi || L.rows > 1;
+    const char* e = std::getenv("FRT_HEAD_KEY0");
+    if (e && std::atoi(e) == 0) multi = false;
+    return d > 0 || h->S.cfg.use_gi || h->strip_views > 0 || multi;
+}
+
+// the level's shadow-pass view for the frame being rendered (its key column allocated on first use)
+static int set_level_head(frt_scene_handle* h, size_t d) {
+    auto& L = h->levels[d];
+    if (L.cap <= 0) return 0;
+    if (level_keyed(h, d) && L.head_key == nullptr)
+        FRT_HIP(hipMalloc((void**)&L.head_key, (size_t)L.cap * sizeof(uint64_t)));
+    L.rec.head.op = L.head_op;
+    L.rec.head.key = level_keyed(h, d) ? L.head_key : nullptr;
+    L.rec.head.mat = L.rec.core.w;
+    L.rec.head.cap = L.cap;
+    L.rec.head.node0 = 0;
+    return 0;
+}
+
 static int ensure_level(frt_scene_handle* h, size_t d, int64_t need) {
     auto& L = h->levels[d];
     if (need <= L.cap) return 0;
     int64_t nc = std::max<int64_t>(need, L.cap * 2);
     hip_ignore(hipFree(L.rec.core.w));
-    hip_ignore(hipFree(L.head));
-    L.head = nullptr;
+    hip_ignore(hipFree(L.head_op));
+    hip_ignore(hipFree(L.head_key));
+    L.head_op = nullptr;
+    L.head_key = nullptr;
     hip_ignore(hipFree(L.q));
     hip_ignore(hipFree(L.surface.w));
     hip_ignore(hipFree(L.child.w));
@@ -3836,8 +3858,7 @@ static int ensure_level(frt_scene_handle* h, size_t d, int64_t need) {
         L.rec.root = d == 0 ? 1 : 0;
         L.rec.eye_cam = level_eye_cam(h, d);
     }
-    FRT_HIP(hipMalloc((void**)&L.head, nc * sizeof(frt::ShadowHead)));
-    L.rec.head = L.head;
+    FRT_HIP(hipMalloc((void**)&L.head_op, (size_t)nc * 3 * sizeof(double)));
     FRT_HIP(hipMalloc((void**)&L.q, nc * sizeof(frt::QueuedRay)));
     FRT_HIP(hipMalloc((void**)&L.surface.w, frt::Cols<frt::Tri9>::bytes(nc)));
     L.surface.cap = nc;
@@ -3847,7 +3868,7 @@ static int ensure_level(frt_scene_handle* h, size_t d, int64_t need) {
     FRT_HIP(hipMalloc((void**)&L.counts, nc * std::max(1, h->S.num_lights) * sizeof(int32_t)));
     if (h->shade_stage) FRT_HIP(hipMalloc((void**)&L.spos, nc * sizeof(uint32_t)));
     L.cap = nc;
-    return 0;
+    return set_level_head(h, d);
 }
 
 static inline unsigned grid_for(int64_t n, int block = frt::kBlock) { return (unsigned)((n + block - 1) / block); }
@@ -3996,14 +4017,14 @@ static void launch_trace(frt_scene_handle* h, const frt::Batch& B, const frt::Qu
 }
 
 template <int F>
-static void launch_shadow_f(frt_scene_handle* h, const frt::Batch& B, const frt::ShadowHead* rec, int64_t n, int32_t* counts) {
+static void launch_shadow_f(frt_scene_handle* h, const frt::Batch& B, const frt::HeadCols& rec, int64_t n, int32_t* counts) {
     const int64_t work = n * h->samples_per_node;
     hipLaunchKernelGGL(frt::k_shadow<F>, dim3(grid_for(work, frt::kTraceBlock)), dim3(frt::kTraceBlock), h->lds_bytes,
                        h->stream, h->S, B, rec, n, h->j_light, h->j_point, h->samples_per_node, counts, h->err);
 }
 
 template <int F>
-static void launch_shadow_redo_f(frt_scene_handle* h, const frt::Batch& B, const frt::ShadowHead* rec, int64_t n,
+static void launch_shadow_redo_f(frt_scene_handle* h, const frt::Batch& B, const frt::HeadCols& rec, int64_t n,
                                  int32_t* counts) {
     hipLaunchKernelGGL(frt::k_shadow_redo<F>, dim3(64), dim3(frt::kTraceBlock), h->lds_bytes, h->stream, h->S, B, rec, n,
                        h->j_light, h->j_point, h->samples_per_node, counts, h->err, h->redo, h->redo_count, h->redo_cap);
@@ -4027,7 +4048,7 @@ static uint64_t seg_table(const PinnedBuf<unsigned>& host_mcount, uint32_t segca
 }
 
 // (node0: the first node's index in the level, for its tile box)
-static void launch_shadow(frt_scene_handle* h, const frt::Batch& B, const frt::ShadowHead* rec, int64_t n, int32_t* counts,
+static void launch_shadow(frt_scene_handle* h, const frt::Batch& B, const frt::HeadCols& rec, int64_t n, int32_t* counts,
                           int64_t node0 = 0) {
     if (h->jit_shadow) {
         // scene-specialised kernels: the pair kernels decide whole (node, light part) pairs — frt_jit_tile
@@ -4040,8 +4061,8 @@ static void launch_shadow(frt_scene_handle* h, const frt::Batch& B, const frt::S
         int64_t NP = 0;  // parts of frt_jit_part_size() samples per path node (frt_jit_beam)
         for (const auto& L : h->host_lights) NP += std::max(1, (L.num_samples + frt_jit_part_size() - 1) / frt_jit_part_size());
         // the pair kernel's lane index is 32-bit: batches of more than 2^31 - 1 (node, part) pairs run
-        // as node ranges (the shadow kernels read a node's ShadowHead and write its counts only, so a
-        // range is the same pass over rec + off and counts + off * lights; ranges start at tile boundaries)
+        // as node ranges (the shadow kernels read a node's head words and write its counts only, so a
+        // range is the same pass over rec.at(off) and counts + off * lights; ranges start at tile boundaries)
         // (FRT_JIT_MAX_PAIRS lowers the limit: the tests split small batches this way)
         const char* mp_env = std::getenv("FRT_JIT_MAX_PAIRS");
         const long long mp = mp_env ? std::atoll(mp_env) : 0;
@@ -4076,7 +4097,7 @@ static void launch_shadow(frt_scene_handle* h, const frt::Batch& B, const frt::S
             int64_t per = std::max<int64_t>(1, kMaxPairs / NP);
             if (h->tile > 0) per = std::max<int64_t>(h->tile, per / h->tile * h->tile);
             for (int64_t off = 0; off < n; off += per)
-                launch_shadow(h, B, rec + off, std::min(per, n - off), counts + off * h->S.num_lights, node0 + off);
+                launch_shadow(h, B, rec.at(off), std::min(per, n - off), counts + off * h->S.num_lights, node0 + off);
             return;
         }
         const int64_t npairs = n * NP;
@@ -4352,7 +4373,7 @@ static void launch_shadow(frt_scene_handle* h, const frt::Batch& B, const frt::S
         hip_ignore(hipMemsetAsync(h->redo_count, 0, sizeof(unsigned), h->stream));
         h->rays_walked += total_mixed * lpp;  // (parts of fewer samples count their padding lanes too)
         h->pairs_walked += total_mixed;
-        // (ShadowHeads read: a node per lane group, each of the level's n nodes at most once per launch — the entries of
+        // (head words read: a node per lane group, each of the level's n nodes at most once per launch — the entries of
         // one tile re-read its nodes' records from L2)
         h->heads_walked += std::min<uint64_t>(direct_in ? total_mixed * direct_nodes : total_mixed, (uint64_t)n);
         KTimer tr(h, h->cur_st, 9);
@@ -5191,6 +5212,7 @@ static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* 
     const int32_t nviews = h->strip_views;
     const int64_t npix = nrows * hs * std::max(1, nviews);
     if (!h->levels.empty()) h->levels[0].rec.eye_cam = level_eye_cam(h, 0);
+    if (!h->levels.empty() && set_level_head(h, 0)) return -1;
     const int32_t spp = (int32_t)(h->S.cam.usteps * h->S.cam.vsteps);
     if (spp <= 0) return fail("render: usteps*vsteps must be positive");
     // 8 M samples unless the caller asks for more. Each batch pays the shadow pass's host round trips (the list
@@ -5321,7 +5343,7 @@ static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* 
                     return -1;
                 hipLaunchKernelGGL(h->S.num_patterns > 0 ? k_prepare<true> : k_prepare<false>, dim3(grid_for(n)),
                                    dim3(kBlock), 0, h->stream, h->S, B, q, n, h->hits, hn12,
-                                   L.rec, L.head, N.q, h->counters, h->err, tiles ? h->tbox : nullptr, tl,
+                                   L.rec, N.q, h->counters, h->err, tiles ? h->tbox : nullptr, tl,
                                    subtiles ? h->stbox : nullptr, stl, L.counts, dense ? h->spawn_masks : nullptr,
                                    h->prepare_uniform);
                 FRT_HIP(hipGetLastError());
@@ -5347,17 +5369,17 @@ static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* 
             const uint64_t counters_epoch = h->sync_epoch;
             if (h->S.cfg.include_direct && h->samples_per_node > 0) {
                 KTimer t(h, st, 1);
-                launch_shadow(h, B, L.head, n, L.counts);
+                launch_shadow(h, B, L.rec.head, n, L.counts);
                 FRT_HIP(hipGetLastError());
             }
             if (h->jit_stats && h->S.num_lights > 0) {  // FRT_JIT_STATS: (node, light) counts all-lit / all-shadowed / mixed
                 std::vector<int32_t> hc((size_t)n * h->S.num_lights);
-                std::vector<frt::ShadowHead> hh((size_t)n);
+                std::vector<uint64_t> hh((size_t)n);  // (core word 0: the material in its low half, -1 for a miss)
                 FRT_HIP(hipMemcpyAsync(hc.data(), L.counts, hc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-                FRT_HIP(hipMemcpyAsync(hh.data(), L.head, hh.size() * sizeof(frt::ShadowHead), hipMemcpyDeviceToHost, h->stream));
+                FRT_HIP(hipMemcpyAsync(hh.data(), L.rec.core.w, hh.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
                 FRT_HIP(hipStreamSynchronize(h->stream));
                 for (int64_t i = 0; i < n; ++i) {
-                    if (hh[(size_t)i].material < 0) continue;
+                    if ((int32_t)(uint32_t)hh[(size_t)i] < 0) continue;
                     for (int l = 0; l < h->S.num_lights; ++l) {
                         const int32_t c = hc[(size_t)(i * h->S.num_lights + l)];
                         h->uniform_stats[c == 0 ? 1 : (c == h->host_lights[(size_t)l].num_samples ? 0 : 2)]++;
@@ -5405,7 +5427,7 @@ static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* 
                                            L.counts, h->shade_lit, h->shade_lcount, segcap, h->sort_light, keys, vals,
                                            h->lit_stage);
                     else
-                        hipLaunchKernelGGL(k_lit_rows, dim3(grid_for(n)), dim3(kBlock), 0, h->stream, h->S, B, L.head,
+                        hipLaunchKernelGGL(k_lit_rows, dim3(grid_for(n)), dim3(kBlock), 0, h->stream, h->S, B, L.rec.head,
                                            h->shade_lit, h->shade_lcount, segcap, h->sort_light, keys, vals);
                     // (the listed count on the host: the sort's size)
                     auto& lc = h->host_lcount;
@@ -5565,14 +5587,16 @@ static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* 
         st->hits = hits;
         st->shadow_rays = h->S.cfg.include_direct ? hits * (uint64_t)h->samples_per_node : 0;
         // DESIGN.md byte model of the per-ray shadow kernel: per list entry its 4-byte entry and 4-byte resume word;
-        // per node of an entry its ShadowHead, read once for the entry's rays and at most once per launch for the node
-        // (heads_walked: an entry of the sub-part list holds a tile's 64 nodes, of the node-pair list one), and one
-        // 4-byte count added; with a multi-row light
+        // per node of an entry its head words (HeadCols: the 24-byte over_point and the 8-byte material word; the 8-byte
+        // key too with a multi-row light, whose row it picks, where the level stores keys: every level but a derived
+        // level 0, counted for all as an upper bound), read once for the entry's rays and at most once per launch for
+        // the node (heads_walked: an entry of the sub-part list holds a tile's 64 nodes, of the node-pair list one),
+        // and one 4-byte count added; with a multi-row light
         // each ray's 24-byte point from its node's row (a single-row light's points stay in cache); the generic walk:
-        // per shaded node the ShadowHead + one 4-byte count per light
-        constexpr double kHead = (double)sizeof(frt::ShadowHead);
+        // per shaded node the head words + one 4-byte count per light
         bool multi = false;
         for (const auto& L : h->host_lights) multi = multi || L.rows > 1;
+        const double kHead = multi ? 40.0 : 32.0;
         st->shadow_kernel_bytes = !(h->S.cfg.include_direct && h->samples_per_node > 0) ? 0.0
                                   : h->jit_shadow != nullptr ? (double)h->pairs_walked * 8.0 + (double)h->heads_walked * (kHead + 4.0) +
                                                                    (multi ? 24.0 * (double)h->rays_walked : 0.0)

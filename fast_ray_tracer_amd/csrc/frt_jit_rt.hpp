@@ -5,7 +5,7 @@
 // generated kernel's unshadowed counts equal the generic kernel's.
 #pragma once
 
-#include "frt_shadow.hpp"
+#include "frt_camera.hpp"
 
 namespace frt {
 namespace jit {
@@ -188,10 +188,18 @@ struct Lane32 {
     int light;
     bool valid, live;
     const double* lp;  // the light point (binary64)
-    const double* op;  // the path node's over_point
+    // the path node's over_point: coordinate a at op[a * ocap + node] (the level's HeadCols columns, frt_shadow.hpp)
+    const double* op;
+    int64_t ocap;
 };
 
-__device__ __forceinline__ void lane32(const DevScene& S, const Batch& B, const ShadowHead* __restrict__ shead,
+// the lane's over_point, the three doubles the binary64 ray starts from
+__device__ __forceinline__ void lane_op(const Lane32& L, double* o) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) o[a] = L.op[a * L.ocap + L.node];
+}
+
+__device__ __forceinline__ void lane32(const DevScene& S, const Batch& B, const HeadCols& shead,
                                        uint32_t total, const int32_t* __restrict__ j_light,
                                        const int32_t* __restrict__ j_point, uint32_t spn, uint64_t magic,
                                        uint32_t shift, uint32_t tid, Lane32& L) {
@@ -200,18 +208,19 @@ __device__ __forceinline__ void lane32(const DevScene& S, const Batch& B, const 
     L.node = 0;
     L.light = 0;
     L.lp = L.op = nullptr;
+    L.ocap = 0;
     if (L.valid) {
         L.node = (uint32_t)(((uint64_t)tid * magic) >> shift);
         const uint32_t j = tid - L.node * spn;
         L.light = j_light[j];
         const int pt = j_point[j];
-        const ShadowHead* nr = shead + L.node;
-        if (nr->material >= 0) {
+        if (shead.hit(L.node)) {
             L.live = true;
             const frt_light& lt = S.lights[L.light];
-            const int row = light_row(lt, B.seed, nr->key, L.light, 0);
+            const int row = lt.rows <= 1 ? 0 : light_row(lt, B.seed, head_key(S, B, shead, L.node), L.light, 0);
             L.lp = S.light_points + lt.points + 3 * ((int64_t)row * lt.num_samples + pt);
-            L.op = nr->over_point;
+            L.op = shead.op;
+            L.ocap = shead.cap;
         }
     }
 }
@@ -235,7 +244,11 @@ __device__ __forceinline__ bool ray32v(const double* lp, const double* op, World
     return n2 >= 0x1p-60f && n2 <= 0x1p100f && w.omax <= 0x1p100f;  // (false for NaN)
 }
 
-__device__ __forceinline__ bool ray32(const Lane32& L, World32& w, Iv& dist) { return ray32v(L.lp, L.op, w, dist); }
+__device__ __forceinline__ bool ray32(const Lane32& L, World32& w, Iv& dist) {
+    double op[3];
+    lane_op(L, op);
+    return ray32v(L.lp, op, w, dist);
+}
 
 // (frt_jit_trace) a closest-hit ray in binary32: o~ = f32(o) as above, d~ = f32(d), within u of the reference's
 // binary64 direction, inside the 6.6u the model above allows the world ray, for a direction of unit length
@@ -261,11 +274,12 @@ __device__ __forceinline__ void ray64(const Lane32& L, Ray& r, double& dist) {
         dist = 0.0;
         return;
     }
-    double v[3];
+    double v[3], op[3];
+    lane_op(L, op);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        v[a] = L.lp[a] - L.op[a];
-        r.o[a] = L.op[a];
+        v[a] = L.lp[a] - op[a];
+        r.o[a] = op[a];
     }
     dist = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
     normalize3(v, r.d);
@@ -344,7 +358,7 @@ __device__ __forceinline__ void count_part(const DevScene& S, const Lane32& L, b
 // over the lanes (one per lane for 64-node tiles), instead of one atomic per node and lit lane (up to 64 per lane on
 // the same addresses). Integer sums: the counts are the same. (all lanes of the wave; base, len, lt: the run's first
 // node, its length (uniform) and light)
-__device__ __forceinline__ void add_run_counts(const ShadowHead* __restrict__ shead, int32_t* counts, uint32_t nl,
+__device__ __forceinline__ void add_run_counts(const HeadCols& shead, int32_t* counts, uint32_t nl,
                                                bool add, uint32_t base, uint32_t len, uint32_t lt, int32_t amount,
                                                uint32_t nnodes) {
     const int lane = threadIdx.x & 63;
@@ -360,7 +374,7 @@ __device__ __forceinline__ void add_run_counts(const ShadowHead* __restrict__ sh
         for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
         for (uint32_t n = (uint32_t)lane; n < len; n += 64u) {
             const uint32_t nd = b0 + n;
-            if (nd < nnodes && shead[nd].material >= 0) atomicAdd(counts + nd * nl + l0, v);
+            if (nd < nnodes && shead.hit(nd)) atomicAdd(counts + nd * nl + l0, v);
         }
     }
 }

@@ -66,16 +66,41 @@ __device__ __forceinline__ int64_t queue_slot(const Batch& B, int64_t i) {
     return (int64_t)lo * B.qsegcap + (i - B.qprefix[lo]);
 }
 
-// what the shadow pass reads of a path node, 40 bytes per node (the pass re-reads it from 100 lanes;
-// keeping it apart from the path-node columns keeps its HBM traffic at about one line per node, and the
-// unpadded record keeps k_prepare's writes of it at 40 bytes: a wave stores 20 whole lines)
-struct alignas(8) ShadowHead {
-    double over_point[3];
-    uint64_t key;
-    int32_t material;  // -1: the ray missed
-    int32_t pad;
+// key of sample s of a batch's level 0 (frt_camera.hpp: the key camera_ray gives the sample's ray)
+__device__ __forceinline__ uint64_t camera_key(const DevScene& S, const Batch& B, int64_t s);
+
+// What the shadow pass reads of a level's path nodes, as columns of the level's capacity (the pass re-reads it from
+// 100 lanes; apart from the path-node columns, its HBM traffic stays at about one line per node): over_point as three
+// columns of doubles (coordinate a of node i at op[a * cap + i]: a wave's k_prepare stores are three 512-byte runs)
+// and the nodes' keys where they cannot be derived. A level 0 whose rays are camera_ray's stores no keys (key ==
+// nullptr): node i's is camera_key(S, B, node0 + i). Whether a node has a hit to shade is the material word of its
+// path-node record (NodeCols core word 0, -1 for a miss), which k_prepare writes for every node: mat is that column.
+struct HeadCols {
+    double* op = nullptr;
+    uint64_t* key = nullptr;
+    const uint64_t* mat = nullptr;
+    int64_t cap = 0;
+    int64_t node0 = 0;  // the level's index of the view's node 0 (a node range of the level: at())
+
+    // the nodes from off on (the same columns: the stride stays the level's capacity)
+    __host__ __device__ HeadCols at(int64_t off) const {
+        HeadCols v = *this;
+        v.op += off;
+        if (v.key != nullptr) v.key += off;
+        v.mat += off;
+        v.node0 += off;
+        return v;
+    }
+    __device__ __forceinline__ bool hit(int64_t i) const { return (int32_t)(uint32_t)mat[i] >= 0; }
+    __device__ __forceinline__ void over_point(int64_t i, double* o) const {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) o[a] = op[a * cap + i];
+    }
 };
-static_assert(sizeof(ShadowHead) == 40, "ShadowHead layout");
+
+__device__ __forceinline__ uint64_t head_key(const DevScene& S, const Batch& B, const HeadCols& H, int64_t i) {
+    return H.key != nullptr ? H.key[i] : camera_key(S, B, H.node0 + i);
+}
 
 // one lane per (path node, light sample j); lanes of a node are consecutive
 struct ShadowLane {
@@ -87,7 +112,7 @@ struct ShadowLane {
     bool live;   // the node has a hit to shade
 };
 
-__device__ __forceinline__ void shadow_lane(const DevScene& S, const Batch& B, const ShadowHead* __restrict__ shead,
+__device__ __forceinline__ void shadow_lane(const DevScene& S, const Batch& B, const HeadCols& shead,
                                             int64_t n, const int32_t* __restrict__ j_light,
                                             const int32_t* __restrict__ j_point, int32_t samples_per_node,
                                             int64_t tid, ShadowLane& L) {
@@ -102,18 +127,19 @@ __device__ __forceinline__ void shadow_lane(const DevScene& S, const Batch& B, c
         const int j = (int)(tid % samples_per_node);
         L.light = j_light[j];
         const int pt = j_point[j];
-        const ShadowHead* nr = shead + L.node;
-        if (nr->material >= 0) {
+        if (shead.hit(L.node)) {
             L.live = true;
             const frt_light& lt = S.lights[L.light];
-            const int row = light_row(lt, B.seed, nr->key, L.light, 0);
+            const int row = lt.rows <= 1 ? 0 : light_row(lt, B.seed, head_key(S, B, shead, L.node), L.light, 0);
             const double* lp = S.light_points + lt.points + 3 * ((int64_t)row * lt.num_samples + pt);
             // is_shadowed (renderer.c:74-93)
-            double v[3] = {lp[0] - nr->over_point[0], lp[1] - nr->over_point[1], lp[2] - nr->over_point[2]};
+            double op[3];
+            shead.over_point(L.node, op);
+            double v[3] = {lp[0] - op[0], lp[1] - op[1], lp[2] - op[2]};
             L.distance = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-            L.r.o[0] = nr->over_point[0];
-            L.r.o[1] = nr->over_point[1];
-            L.r.o[2] = nr->over_point[2];
+            L.r.o[0] = op[0];
+            L.r.o[1] = op[1];
+            L.r.o[2] = op[2];
             normalize3(v, L.r.d);
         }
     }
