@@ -563,11 +563,7 @@ __global__ void __launch_bounds__(kTraceBlock) FRT_SHADOW_ATTR k_shadow(DevScene
     // every lane of the wave takes part in the (wave-coherent) walk
     unsigned e = 0;
     double unused;
-#ifdef FRT_EXPERIMENT_NOWALK
-    const bool lit = L.live && L.distance > 0.5;
-#else
     const bool lit = walk<true, kFeat>(S, L.r, L.distance, L.live, unused, frt_walk_smem, e) == 0 && L.live;
-#endif
     if (e) atomicOr(err, e);
     shadow_count(S, L, lit, counts);
 }
@@ -597,24 +593,17 @@ __global__ void __launch_bounds__(kTraceBlock) k_shadow_redo(DevScene S, Batch B
     if (e) atomicOr(err, e);
 }
 
+// (The two compile-time alternates left in shade_node, FRT_SHADE_FACTOR=0 and FRT_SHADE_PAIR=1, are never built. They
+// stay because taking either out changes the register allocation of the compiled shading kernels (what the point
+// lambdas capture): a change for a pull request that measures those kernels again, profiles/r09_device_code_sha.txt.)
 #ifndef FRT_SHADE_FACTOR
 #define FRT_SHADE_FACTOR 1
 #endif
-#ifndef FRT_SHADE_ALG
-#define FRT_SHADE_ALG 1
-#endif
-#ifndef FRT_SHADE_SKIP
-#define FRT_SHADE_SKIP 1
-#endif
-// FRT_SHADE_FMA (default 1): the light point's three dot products (|v|^2, v.n, v.e) as one product and two fused
-// multiply-adds instead of three products and two sums (each within an ulp of the separately rounded sum, like the
-// Newton-refined estimates beside them); 0: the reference's separately rounded operations (A/B builds)
-#ifndef FRT_SHADE_FMA
-#define FRT_SHADE_FMA 1
-#endif
+// the light point's three dot products (|v|^2, v.n, v.e) as one product and two fused multiply-adds instead of three
+// products and two sums (each within an ulp of the separately rounded sum, like the Newton-refined estimates beside
+// them)
 __device__ __forceinline__ double dot3_shade(const double* a, const double* b) {
-    if (FRT_SHADE_FMA) return __builtin_fma(a[0], b[0], __builtin_fma(a[1], b[1], a[2] * b[2]));
-    return dot3(a, b);
+    return __builtin_fma(a[0], b[0], __builtin_fma(a[1], b[1], a[2] * b[2]));
 }
 // a level-0 node's eyev where the level does not store it (NodeCols::eye_cam): prepare_computations' negated ray
 // direction (frt_shade.hpp prepare) of the node's camera ray, the same camera_ray k_prepare traced, bit for bit
@@ -665,12 +654,9 @@ __global__ void __launch_bounds__(kBlock) k_view_rays(DevScene S, Batch B, const
 
 // lighting_microfacet (renderer.c:895-979) per light, summed as shade_hit does (renderer.c:704-725): the
 // A, D, S triples of path node i into out (out[4k + c]: term k, channel c)
-// (lds_row: k_shade_lit's per-wave LDS staging of a multi-row light's row, kLdsPoints points; nullptr elsewhere)
-constexpr int kLdsPoints = 128;
 // (c0 >= 0: the unshadowed count of a scene's one light, staged by the caller; counts[i] is then not read)
 __device__ __forceinline__ void shade_node(const DevScene& S, const Batch& B, const NodeRec& nr, int64_t i,
-                                           const int32_t* __restrict__ counts, double* out, double* lds_row = nullptr,
-                                           int32_t c0 = -1) {
+                                           const int32_t* __restrict__ counts, double* out, int32_t c0 = -1) {
     double sA[3] = {0, 0, 0}, sD[3] = {0, 0, 0}, sS[3] = {0, 0, 0};
     if (S.cfg.include_direct) {
         for (int li = 0; li < S.num_lights; ++li) {
@@ -698,20 +684,18 @@ __device__ __forceinline__ void shade_node(const DevScene& S, const Batch& B, co
                     constexpr bool kFactored = FRT_SHADE_FACTOR != 0;
                     double sum_ldn = 0.0, sum_b = 0.0, sum_fb = 0.0;
                     const double cdist = (nr.Ns + 2) * 0.5 * k1Pi;
-                    // The light vector and the half vector by their shared terms (FRT_SHADE_ALG, default 1): with
+                    // The light vector and the half vector by their shared terms: with
                     // v = p - over_point, m2 = v.v and r = 1/|v|, lightv = v r, so lightv.n = (v.n) r and
                     // lightv.e = (v.e) r; the half vector h = (lightv + e) / |lightv + e| has |lightv + e|^2 =
                     // lightv.lightv + 2 lightv.e + e.e, and n.h, e.h, lightv.h are (n.lightv + n.e) / |..|,
                     // (lightv.e + e.e) / |..|, (lightv.lightv + lightv.e) / |..|: two dot products and a few
                     // multiplies per point instead of the normalised vectors and five dot products (a few ulps
                     // from vector_normalize's path, like the reciprocal estimates; ned = n.e is the node's).
-                    // FRT_SHADE_ALG=0 builds: the vectors as the reference forms them (A/B runs).
-                    constexpr bool kAlg = FRT_SHADE_ALG != 0;
                     const double ee = dot3(nr.eyev, nr.eyev);
                     // pow_ns's exponent test once per node (the same Ns for every point: pow_plan / pow_apply)
                     const double nsd = nr.Ns;
                     const PowPlan pplan = pow_plan(nsd);
-                    // The specular tail (FRT_SHADE_SKIP, default 1): with Ns = 200 the lobe (n.h)^Ns is below 2^-60 of
+                    // The specular tail: with Ns = 200 the lobe (n.h)^Ns is below 2^-60 of
                     // the point's diffuse term for most (node, point) pairs, yet every lane paid the reciprocal, the
                     // power and the quotient. A point's specular terms are at most (|Ks| + |1 - Ks|) I brdf per channel
                     // (F <= 1: 0 <= 1 - l.h <= 1), brdf <= cdist (n.h)^Ns / (4 (l.n) (n.e)) (G <= 1), and its diffuse
@@ -722,8 +706,8 @@ __device__ __forceinline__ void shade_node(const DevScene& S, const Batch& B, co
                     // v_log_f32 are within 1e-4 of a binade at Ns <= 4096). Per lane: a lane's result does not
                     // depend on its wave; the arithmetic is skipped where every lane of the wave skips.
                     float skip_c = __builtin_huge_valf();  // log2(cdist / (rK (n.e))) + 62 + 4; +inf: never skip
-                    if (FRT_SHADE_SKIP && kFactored && kAlg && S.cfg.include_diffuse && S.cfg.include_spec_highlight &&
-                        nsd >= 2.0 && nsd <= 4096.0 && ned > 0x1p-100) {
+                    if (kFactored && S.cfg.include_diffuse && S.cfg.include_spec_highlight && nsd >= 2.0 && nsd <= 4096.0 &&
+                        ned > 0x1p-100) {
                         double rk = 1.0;
                         for (int k = 0; k < 3; ++k) rk = fmin(rk, nr.Kd[k] / (fabs(nr.Ks[k]) + fabs(1.0 - nr.Ks[k])));
                         if (rk > 0x1p-100) skip_c = __log2f((float)(cdist / (rk * ned))) + 66.0f;
@@ -732,15 +716,9 @@ __device__ __forceinline__ void shade_node(const DevScene& S, const Batch& B, co
                     // one light point's terms (lp: the point)
                     auto term = [&](const double* lp) {
                         double diff[3] = {lp[0] - nr.over_point[0], lp[1] - nr.over_point[1], lp[2] - nr.over_point[2]};
-                        double lv[3] = {0.0, 0.0, 0.0}, ldn, m2 = 0.0, rl = 0.0;
-                        if (kAlg) {
-                            m2 = dot3_shade(diff, diff);
-                            rl = rsqrt_shade(m2);
-                            ldn = dot3_shade(diff, nr.normalv) * rl;
-                        } else {
-                            normalize3_shade(diff, lv);
-                            ldn = dot3(lv, nr.normalv);
-                        }
+                        const double m2 = dot3_shade(diff, diff);
+                        const double rl = rsqrt_shade(m2);
+                        const double ldn = dot3_shade(diff, nr.normalv) * rl;
                         if (S.cfg.include_diffuse && ldn >= 0.0) {
                             if (kFactored) {
                                 sum_ldn += ldn;
@@ -753,9 +731,9 @@ __device__ __forceinline__ void shade_node(const DevScene& S, const Batch& B, co
                             }
                         }
                         if (S.cfg.include_spec_highlight && ldn >= 0.0) {
-                            double ndl, ndh, edh, ldh;
-                            if (kAlg) {
-                                ndl = ldn;
+                            const double ndl = ldn;
+                            double ndh, edh, ldh;
+                            {  // (el, ll, rh and the tail test in a scope of their own: the compiled loop is the one measured)
                                 const double el = dot3_shade(diff, nr.eyev) * rl, ll = (m2 * rl) * rl;
                                 const double rh = rsqrt_shade(ll + 2.0 * el + ee);
                                 ndh = fmax(0.0, (ldn + ned) * rh);
@@ -766,13 +744,6 @@ __device__ __forceinline__ void shade_node(const DevScene& S, const Batch& B, co
                                                   nsf * __log2f((float)ndh) - 2.0f * __log2f((float)ldn) + skip_c < 0.0f;
                                 if (__ballot(!tail) == 0ull) return;
                                 if (tail) return;
-                            } else {
-                                ndl = dot3(nr.normalv, lv);
-                                double tmp[3] = {lv[0] + nr.eyev[0], lv[1] + nr.eyev[1], lv[2] + nr.eyev[2]}, hv[3];
-                                normalize3_shade(tmp, hv);
-                                ndh = fmax(0.0, dot3(nr.normalv, hv));
-                                edh = fmax(0.0, dot3(nr.eyev, hv));
-                                ldh = dot3(lv, hv);
                             }
                             double dist_term = kFactored ? pow_apply(ndh, nsd, pplan) * cdist
                                                          : (nr.Ns + 2) * pow_ns(ndh, nr.Ns) * 0.5 * k1Pi;
@@ -803,7 +774,7 @@ __device__ __forceinline__ void shade_node(const DevScene& S, const Batch& B, co
 #ifndef FRT_SHADE_PAIR
 #define FRT_SHADE_PAIR 0
 #endif
-                    constexpr bool kPair = FRT_SHADE_PAIR && kAlg && kFactored && FRT_SHADE_FAST;
+                    constexpr bool kPair = FRT_SHADE_PAIR && kFactored && FRT_SHADE_FAST;
                     // the specular terms of one point past its tail test (term()'s arithmetic)
                     auto spec_rest = [&](double ndl, double ndh, double edh, double ldh) {
                         const double dist_term = pow_apply(ndh, nsd, pplan) * cdist;
@@ -860,14 +831,7 @@ __device__ __forceinline__ void shade_node(const DevScene& S, const Batch& B, co
                     // through the scalar cache (the point's coordinates in SGPRs, no vector memory latency)
                     // (the constant address space: without it the compiler cannot prove that nothing the kernel stores
                     // aliases the points, and emits vector flat loads of the uniform address, waited on every point)
-#ifndef FRT_SHADE_CONST_PTS
-#define FRT_SHADE_CONST_PTS 1
-#endif
-#if FRT_SHADE_CONST_PTS
                     using const_pts = const __attribute__((address_space(4))) double*;
-#else
-                    using const_pts = const double*;
-#endif
                     auto uniform_points = [&](const double* up) {
                         const const_pts sp = (const_pts)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(
                                                               (int)(uint32_t)(uint64_t)up)) |
@@ -904,28 +868,12 @@ __device__ __forceinline__ void shade_node(const DevScene& S, const Batch& B, co
                     const int ra = __builtin_amdgcn_readfirstlane(row);
                     if (L.rows <= 1) {
                         uniform_points(row0);  // one cache row
-                    } else if (__ballot(row != ra) == 0ull && lds_row != nullptr) {
-                        // the wave shares its row (the lit list in row order): the row into the wave's LDS in one
-                        // coalesced round trip by the active lanes, then every lane reads the same point (a broadcast).
-                        // (Measured slower than the scalar loads below once those were real scalar loads: the LDS
-                        // reads' latency is paid on every point, the scalar loads run a point ahead.)
-                        const double* rp = row0 + 3 * (int64_t)ra * ns;
-                        const unsigned long long act = __ballot(true);
-                        const int lane = (int)(threadIdx.x & 63);
-                        const int rank = __popcll(act & ((1ull << lane) - 1)), nact = __popcll(act);
-                        for (int c0 = 0; c0 < ns; c0 += kLdsPoints) {
-                            const int cn = min(kLdsPoints, ns - c0);
-                            __builtin_amdgcn_wave_barrier();
-                            for (int w = rank; w < 3 * cn; w += nact) lds_row[w] = rp[3 * c0 + w];
-                            __builtin_amdgcn_wave_barrier();
-                            __builtin_amdgcn_s_waitcnt(0xc07f);  // (lgkmcnt(0): the stores are done before the reads)
-                            for (int p = 0; p < cn; ++p) {
-                                const double lp[3] = {lds_row[3 * p], lds_row[3 * p + 1], lds_row[3 * p + 2]};
-                                term(lp);
-                            }
-                        }
                     } else if (__ballot(row != ra) == 0ull) {
-                        uniform_points(row0 + 3 * (int64_t)ra * ns);  // (the wave shares its row)
+                        // the wave shares its row (the lit list in row order): through the scalar cache like the
+                        // single-row light's points. Staging the row through LDS lost to it, 14.2 -> 13.1 ms per shipped
+                        // frame (profiles/r05_ab_shade_scalar_rows.txt): the LDS reads' latency is paid on every point,
+                        // the scalar loads run a point ahead.
+                        uniform_points(row0 + 3 * (int64_t)ra * ns);
                     } else {
                         // the node's own row (per lane): each point's loads issued two points ahead of its arithmetic
                         // (the rows are scattered over the 157 MB cache, so a load's latency is a trip to HBM or MALL)
@@ -1012,7 +960,7 @@ __device__ __forceinline__ void shade_node32(const DevScene& S, const Batch& B, 
                 Q.cdist = (nr.Ns + 2) * 0.5 * k1Pi;
                 // (shade_node's specular tail constant, from the same binary64 values)
                 float skip_c = __builtin_huge_valf();
-                if (FRT_SHADE_SKIP && S.cfg.include_diffuse && S.cfg.include_spec_highlight && Q.ns >= 2.0 &&
+                if (S.cfg.include_diffuse && S.cfg.include_spec_highlight && Q.ns >= 2.0 &&
                     Q.ns <= 4096.0 && Q.ned > 0x1p-100) {
                     double rk = 1.0;
                     for (int k = 0; k < 3; ++k) rk = fmin(rk, nr.Kd[k] / (fabs(nr.Ks[k]) + fabs(1.0 - nr.Ks[k])));
@@ -1289,7 +1237,11 @@ __global__ void __launch_bounds__(kBlock) k_lit_stage(DevScene S, Batch B, NodeC
 #ifndef FRT_SHADE_WAVES
 #define FRT_SHADE_WAVES 4
 #endif
-// (kRows: the list in light-row order, a multi-row light's row staged per wave in LDS)
+// k_shade_lit's block: one wave (9.15 -> 8.83 ms per headline frame, profiles/r05_ab_shade_block.txt; <= kBlock)
+#ifndef FRT_SHADE_LIT_BLOCK
+#define FRT_SHADE_LIT_BLOCK 64
+#endif
+// (kRows: the list in light-row order, so a wave shares its multi-row light's row)
 // (kFast32: the body of k_shade_lit32, the light-point loops in binary32 from F; everything else is shared)
 template <bool kRows, bool kFast32>
 __device__ __forceinline__ void shade_lit_body(const DevScene& S, const Batch& B, const NodeCols& rec,
@@ -1367,18 +1319,10 @@ __device__ __forceinline__ void shade_lit_body(const DevScene& S, const Batch& B
         }
     }
     double out[12];
-// FRT_SHADE_LDS_ROWS=1: a wave's shared row staged through LDS (A/B runs). 0 (default): read through the scalar
-// cache like the single-row light's points, 14.2 -> 13.1 ms per shipped frame (profiles/r05_ab_shade_scalar_rows.txt)
-#ifndef FRT_SHADE_LDS_ROWS
-#define FRT_SHADE_LDS_ROWS 0
-#endif
     if constexpr (kFast32) {
         shade_node32(S, B, F, nr, i, counts, out, c0);
-    } else if (kRows && FRT_SHADE_LDS_ROWS) {
-        __shared__ double lds_rows[kBlock / 64][3 * kLdsPoints];  // (a multi-row light's row per wave, 3 KB)
-        shade_node(S, B, nr, i, counts, out, lds_rows[threadIdx.x >> 6], c0);
     } else {
-        shade_node(S, B, nr, i, counts, out, nullptr, c0);
+        shade_node(S, B, nr, i, counts, out, c0);
     }
     if (sorted_out) {
         uint64_t* dst = surface.w + (size_t)9 * m;  // (the level's surface memory as 9-word records, sorted order)
@@ -1513,13 +1457,7 @@ __global__ void __launch_bounds__(kFuseBlock) k_combine_resolve(DevScene S, cons
                                                                 const uint32_t* __restrict__ spos) {
     // (each pixel's column sum goes back into the first slot of the run it was summed from: only the thread that
     // summed a run reads it, and the block's LDS stays at 18.5 KB, so six blocks fit a CU instead of four)
-#ifndef FRT_RESOLVE_INPLACE
-#define FRT_RESOLVE_INPLACE 1
-#endif
     __shared__ double stage[9][kFuseBlock + 1];
-#if !FRT_RESOLVE_INPLACE
-    __shared__ double sum_sep[9][kFuseBlock];
-#endif
     const int t = threadIdx.x;
     const int64_t p0 = (int64_t)blockIdx.x * ppb;
     const int64_t i = p0 * spp + t;
@@ -1537,18 +1475,10 @@ __global__ void __launch_bounds__(kFuseBlock) k_combine_resolve(DevScene S, cons
         const double* st = stage[f] + lp * spp;
         double acc = 0.0;
         for (int kk = 0; kk < spp; ++kk) acc += st[kk];
-#if FRT_RESOLVE_INPLACE
         stage[f][lp * spp] = acc * (1.0 / (double)spp);
-#else
-        sum_sep[f][lp] = acc * (1.0 / (double)spp);
-#endif
     }
     __syncthreads();
-#if FRT_RESOLVE_INPLACE
     auto sum = [&](int f, int lp) { return stage[f][lp * spp]; };
-#else
-    auto sum = [&](int f, int lp) { return sum_sep[f][lp]; };
-#endif
     for (int q = t; q < ppb * 4; q += kFuseBlock) {
         const int lp = q >> 2, f = q & 3;
         const int64_t p = p0 + lp;
@@ -2232,6 +2162,8 @@ struct PinnedBuf {
 
 struct frt_scene_handle {
     int device = 0;
+    UploadKnobs up;  // the FRT_* knobs of this upload (frt_knobs.hpp)
+    FrameKnobs fk;   // ... and of the frame being rendered (read at render_impl's entry)
     frt::DevScene S{};
     std::vector<void*> owned;
     std::vector<double> host_table;  // the non-jittered CMJ table on the device (frt_scene_set_camera compares it)
@@ -2246,10 +2178,10 @@ struct frt_scene_handle {
     void* jit_beam = nullptr;          // its pair kernel (frt_jit_beam)
     void* jit_tile = nullptr;          // tile pair kernel (frt_jit_tile) and its listed tiles' node pairs
     void* jit_list = nullptr;          //   (frt_jit_beam_list); null: frt_jit_beam decides every pair
-    int tile = 0;                      // path nodes per tile (frt_jit_tile_size), 0 without the tile kernels
+    int tile = 0;                      // path nodes per tile (up.jit_tile), 0 without the tile kernels
     uint64_t scene_key = 0;            // hash of the flattened scene's content (shared photon maps)
     void* jit_sub = nullptr;           // sub-part pair kernel (frt_jit_sub); null: the node pairs' rays are walked
-    int sub = 0;                       // sub-parts per part (frt_jit_sub_count) with jit_sub, else 0
+    int sub = 0;                       // sub-parts per part (up.jit_sub) with jit_sub, else 0
     int sub_ps = 0;                    // samples per sub-part slot (frt_jit_sub_ps)
     const int32_t* light_psamp2 = nullptr;  // the sub-parts' samples (frt_jit_light_subparts), -1 padded
     const float* light_sbox = nullptr;      // the sub-parts' boxes over every cache row, binary32 outward
@@ -2260,12 +2192,7 @@ struct frt_scene_handle {
     void* jit_trace = nullptr;         // closest-hit kernel (frt_jit_trace); null: k_trace for every ray
     int32_t* tredo = nullptr;          // rays frt_jit_trace hands to the generic walk (k_trace_redo), + counter
     int64_t tredo_cap = 0;
-    int subtile = 0;                   // path nodes per sub-tile (frt_jit_subtile_size) with jit_subtile, else 0
-    // the (node, sample) pairs the sub-part / sub-tile stages leave: decided by frt_jit_beam_list one node beam per
-    // lane (FRT_JIT_NODE_BEAM=1), or walked by frt_jit_shadow directly (the default: a node's beam to one sample is
-    // one ray, and the per-ray walk costs a third of the beam walk's instructions; round 5, profiles/r05_ab_nodebeam.txt:
-    // headline 41.5 -> 36.4 ms, shipped light 90.5 -> 76.4 ms)
-    bool node_beam = false;
+    int subtile = 0;                   // path nodes per sub-tile (up.jit_subtile) with jit_subtile, else 0
     float* stbox = nullptr;            // the level's sub-tile boxes (k_prepare): 6 floats per sub-tile
     int64_t stbox_cap = 0;
     uint32_t* s2list = nullptr;        // the sub-tile pairs left mixed (frt_jit_subtile's list)
@@ -2276,7 +2203,7 @@ struct frt_scene_handle {
     uint32_t* tlist = nullptr;         // undecided (tile, light part) pairs, kMixSegs segments
     int64_t tlist_cap = 0;
     uint64_t tile_pairs = 0, tile_mixed = 0, node_pairs = 0, node_mixed = 0;  // this frame's pair-kernel counts
-    bool jit_beam_on = true;           // FRT_JIT_BEAM=0: every pair is walked ray by ray (A/B)
+    bool jit_beam_on = true;           // up.jit_beam, until a pair kernel's launch fails: every pair walked ray by ray
     const int32_t* light_psamp = nullptr;  // the parts' samples (frt_jit_light_parts), -1 padded
     const float* light_aabb = nullptr; // per light, per cache row: the points' box (binary32, outward)
     uint32_t* mixed = nullptr;         // mixed (node, light) pairs, kMixSegs segments
@@ -2301,7 +2228,7 @@ struct frt_scene_handle {
     // the lit list in row order (k_shade -> k_lit_rows -> radix sort) for a multi-row light: the listed nodes' rows
     // (keys, and the sort's alternate buffer), the ordered list (and the unsorted values)
     int sort_light = -1;               // the first light with more than one cache row (FRT_SHADE_SORT=0: none)
-    int shade_stage = 0;               // its shading from staged records / into row order (FRT_SHADE_STAGE)
+    int shade_stage = 0;               // its shading from staged records / into row order (up.shade_stage), else 0
     uint32_t* lit_row = nullptr;
     int64_t lit_row_cap = 0;
     uint32_t* lit_flat = nullptr;
@@ -2312,10 +2239,7 @@ struct frt_scene_handle {
     // (ensure_light32: built by the handle's first fast frame, so a parity-only handle never holds them)
     bool fast32 = false;
     frt::Light32 light32{nullptr, nullptr};
-    int queue_sort = 2;                 // a level's queue in parent order (FRT_QUEUE_SORT: 2 dense, 1 sorted, 0 off)
-    int queue_sort_shift = 0;           // (FRT_QUEUE_SORT_SHIFT)
-    int prepare_uniform = 1;            // k_prepare's scalar path for waves that hit one leaf (FRT_PREPARE_UNIFORM=0: off)
-    uint32_t* qsort = nullptr;          // (its keys, their alternate buffer and the storage slots, 3 words per entry)
+    uint32_t* qsort = nullptr;          // (the queue sort's keys, their alternate buffer and the storage slots, 3 words per entry)
     int64_t qsort_cap = 0;
     unsigned long long* spawn_masks = nullptr;  // (FRT_QUEUE_SORT=2: the next level's taken slots, k_prepare)
     int64_t spawn_masks_cap = 0;
@@ -2618,11 +2542,10 @@ struct MeshBuild {
 };
 
 // the scene's mesh roots (host): see kMeshMinTris above
-static std::vector<int> mesh_roots(const frt_scene* sc) {
+static std::vector<int> mesh_roots(const frt_scene* sc, const UploadKnobs& K) {
     const int nn = sc->num_nodes;
     std::vector<int> roots;
-    const char* env = std::getenv("FRT_MESH");  // FRT_MESH=0: the plain walk everywhere (A/B runs)
-    if (nn <= 512 || (env && std::strcmp(env, "0") == 0)) return roots;
+    if (nn <= 512 || !K.mesh) return roots;
     auto is_tri = [&](int i) { return sc->nodes[i].type == FRT_TRIANGLE || sc->nodes[i].type == FRT_SMOOTH_TRIANGLE; };
     // inner[i]: node i may sit inside a mesh (a triangle or a group without transform of such nodes)
     std::vector<char> inner((size_t)nn, 0), in_csg((size_t)nn, 0);
@@ -2701,7 +2624,7 @@ static int build_meshes(frt_scene_handle* h, const frt_scene* sc, std::vector<fr
     S.meshes = nullptr;
     S.num_meshes = 0;
     S.mesh_stack = 0;
-    const std::vector<int> roots = mesh_roots(sc);
+    const std::vector<int> roots = mesh_roots(sc, h->up);
     if (roots.empty()) return 0;
     std::vector<MeshBuild> mb = mesh_build(sc, roots);
     std::vector<frt::MeshDesc> desc(roots.size());
@@ -2935,10 +2858,11 @@ static void build_walk_nodes(const frt_scene* sc, std::vector<frt::WalkNode>& wn
 // shadow kernel of a flattened scene without a device. Returns 0 compiled, 1 not eligible, -1 compile error;
 // `log` receives the reason / compiler log, `src` (if non-null) the generated source.
 int frt_jit_check(const frt_scene* sc, char* log, size_t log_cap, char* src, size_t src_cap) {
+    const UploadKnobs K = read_upload_knobs();
     std::vector<frt::WalkNode> wn;
     build_walk_nodes(sc, wn);
     std::string why, clog;
-    const std::string code = frt_jit_shadow_source(wn.data(), sc->num_nodes, sc->roots, sc->num_roots, sc->lights, sc->num_lights, why);
+    const std::string code = frt_jit_shadow_source(wn.data(), sc->num_nodes, sc->roots, sc->num_roots, sc->lights, sc->num_lights, K, why);
     auto put = [](char* dst, size_t cap, const std::string& v) {
         if (dst && cap) {
             std::snprintf(dst, cap, "%s", v.c_str());
@@ -2949,7 +2873,7 @@ int frt_jit_check(const frt_scene* sc, char* log, size_t log_cap, char* src, siz
         put(log, log_cap, why);
         return 1;
     }
-    const int rc = frt_jit_compile_only(code, "gfx950", clog);
+    const int rc = frt_jit_compile_only(code, "gfx950", K, clog);
     put(log, log_cap, clog);
     return rc == 0 ? 0 : -1;
 }
@@ -2979,7 +2903,7 @@ __global__ void k_math_selftest(int64_t n, uint64_t seed, unsigned long long* ba
         const double s = sqrt(m2);
         b += __double_as_longlong(frt::sqrt_core(m2)) != __double_as_longlong(s);
         b += __double_as_longlong(frt::recip_core(s)) != __double_as_longlong(1.0 / s);
-        // the shading's approximations (FRT_SHADE_NEWTON steps): reciprocal magnitude, reciprocal and
+        // the shading's approximations (one Newton step each): reciprocal magnitude, reciprocal and
         // quotient within 2^-46 relative of 1.0 / sqrt(), 1.0 / y and a / y
         const double inv = 1.0 / s;
         b += !(fabs(frt::rsqrt_nr(m2) - inv) <= 0x1p-46 * inv);
@@ -3002,7 +2926,7 @@ __global__ void k_math_selftest(int64_t n, uint64_t seed, unsigned long long* ba
 // triangles in exactly one leaf; every child box contains its triangles' vertices and its children's
 // boxes; every child's smallest pre-order index right), else the number of violations.
 int frt_mesh_check(const frt_scene* sc, int64_t* out, int n) {
-    const std::vector<int> roots = mesh_roots(sc);
+    const std::vector<int> roots = mesh_roots(sc, read_upload_knobs());
     const std::vector<MeshBuild> mb = mesh_build(sc, roots);
     int64_t stats[4] = {(int64_t)roots.size(), 0, 0, 0};
     int64_t bad = 0;
@@ -3234,8 +3158,8 @@ void frt_host_pinned_free(void* p) {
 }
 
 int frt_device_warmup(int device) {
-    // (FRT_WARMUP_TRACE: each step's time to stderr)
-    static const bool trace = std::getenv("FRT_WARMUP_TRACE") != nullptr;
+    const WarmupKnobs K = read_warmup_knobs();
+    const bool trace = K.trace;  // (each step's time to stderr)
     auto t0 = std::chrono::steady_clock::now();
     auto mark = [&](const char* what) {
         if (!trace) return;
@@ -3256,9 +3180,8 @@ int frt_device_warmup(int device) {
     if (hipMalloc(&p, 1 << 20) == hipSuccess) {
         mark("hipMalloc");
         hipStream_t s = nullptr;
-        // (FRT_WARMUP_MODE=1: the null stream instead of a stream of its own, probes only)
-        static const int wmode = std::getenv("FRT_WARMUP_MODE") ? std::atoi(std::getenv("FRT_WARMUP_MODE")) : 0;
-        if (wmode == 1 || hipStreamCreate(&s) == hipSuccess) {  // (the handle's kind of stream: it may take it)
+        // (mode 1: the null stream instead of a stream of its own, probes only)
+        if (K.mode == 1 || hipStreamCreate(&s) == hipSuccess) {  // (the handle's kind of stream: it may take it)
             mark("stream");
             unsigned host[64] = {0};
             hip_ignore(hipMemcpyAsync(p, host, sizeof(host), hipMemcpyHostToDevice, s));
@@ -3304,6 +3227,8 @@ int frt_scene_upload(const frt_scene* sc, int device, frt_scene_handle** out) {
     FRT_HIP(hipSetDevice(device));
     frt_scene_handle* h = new frt_scene_handle();
     h->device = device;
+    h->up = read_upload_knobs();
+    const UploadKnobs& K = h->up;
     frt::DevScene& S = h->S;
     int rc = 0;
     if (sc->config.trace_caustic_map || sc->config.trace_global_map) {
@@ -3383,14 +3308,13 @@ int frt_scene_upload(const frt_scene* sc, int device, frt_scene_handle** out) {
             return -1;
         }
         S.wn = upload(h, wn.data(), wn.size(), rc);
-        const char* jit_env = std::getenv("FRT_JIT");
-        if (rc == 0 && sc->config.include_direct && !(jit_env && std::strcmp(jit_env, "0") == 0)) {
+        if (rc == 0 && sc->config.include_direct && K.jit) {
             std::string why, log;
             phase(2);
-            const std::string src = frt_jit_shadow_source(wn.data(), sc->num_nodes, sc->roots, sc->num_roots, sc->lights, sc->num_lights, why);
+            const std::string src = frt_jit_shadow_source(wn.data(), sc->num_nodes, sc->roots, sc->num_roots, sc->lights, sc->num_lights, K, why);
             phase(3);
             FrtJitFns fns;
-            if (!src.empty() && frt_jit_compile(src, h->device, fns, log) != 0) {
+            if (!src.empty() && frt_jit_compile(src, h->device, K, fns, log) != 0) {
                 why = "hiprtc: " + log.substr(0, 2000);
                 fns = FrtJitFns{};
             }
@@ -3405,16 +3329,13 @@ int frt_scene_upload(const frt_scene* sc, int device, frt_scene_handle** out) {
             h->jit_beam = fns.beam;
             h->jit_tile = fns.tile;
             h->jit_list = fns.list;
-            h->tile = fns.tile && fns.list ? frt_jit_tile_size() : 0;
+            h->tile = fns.tile && fns.list ? K.jit_tile : 0;
             h->jit_sub = fns.sub;
-            h->sub = fns.sub ? frt_jit_sub_count() : 0;
+            h->sub = fns.sub ? K.jit_sub : 0;
             h->jit_subtile = fns.subtile;
             // (the closest-hit kernel writes n1 = n2 = 1: scenes with refractive indices other than one keep k_trace)
             h->jit_trace = sc->config.all_ni_one ? fns.trace : nullptr;
-            h->subtile = fns.subtile ? frt_jit_subtile_size() : 0;
-            // (multi-row lights get no sub-tile kernel unless FRT_JIT_SUBTILE asks for one, frt_jit_shadow_source: the
-            // stage cut the shipped frame's per-ray lanes by 11 % for 6.5 ms; without it 76.4 -> 72.1 ms,
-            // profiles/r05_ab_nodebeam.txt)
+            h->subtile = fns.subtile ? K.jit_subtile : 0;
             if (h->jit_shadow) {
                 h->redo_cap = 1u << 20;
                 void* p = nullptr;
@@ -3425,8 +3346,7 @@ int frt_scene_upload(const frt_scene* sc, int device, frt_scene_handle** out) {
                 h->owned.push_back(p);
                 h->redo = (int64_t*)p;
                 h->redo_count = (unsigned*)(h->redo + h->redo_cap);
-                const char* beam_env = std::getenv("FRT_JIT_BEAM");
-                h->jit_beam_on = !(beam_env && std::strcmp(beam_env, "0") == 0);
+                h->jit_beam_on = K.jit_beam;
                 // each light's parts (frt_jit_light_parts) and, per cache row, the box of each part's points,
                 // rounded outward to binary32; with a multi-row light (the shipped area-light cache) also, after
                 // every light's row boxes, each part's box over all rows (the tile kernel's: a tile's nodes draw
@@ -3435,7 +3355,7 @@ int frt_scene_upload(const frt_scene* sc, int device, frt_scene_handle** out) {
                 // union stays the size of the part's cells.
                 std::vector<float> box;
                 std::vector<int32_t> psamp;
-                const int PS = frt_jit_part_size();
+                const int PS = K.jit_part;
                 auto push_box = [](std::vector<float>& v, const double* pl, const double* ph) {
                     for (int a = 0; a < 3; ++a) {
                         float f = (float)pl[a];
@@ -3491,10 +3411,6 @@ int frt_scene_upload(const frt_scene* sc, int device, frt_scene_handle** out) {
                 }
                 h->light_psamp = upload(h, psamp.data(), psamp.size(), rc);
                 h->light_aabb = upload(h, box.data(), box.size(), rc);
-                {
-                    const char* nb = std::getenv("FRT_JIT_NODE_BEAM");
-                    h->node_beam = nb && std::atoi(nb) != 0;
-                }
                 if (h->sub > 0) {  // the sub-parts: samples and boxes (over every cache row) by (global part, sub-part)
                     std::vector<int32_t> ps2;
                     std::vector<float> sbox;
@@ -3523,7 +3439,7 @@ int frt_scene_upload(const frt_scene* sc, int device, frt_scene_handle** out) {
                     frt_scene_release(h);
                     return fail("frt_scene_upload: pinned host buffer allocation failed");
                 }
-                if (std::getenv("FRT_JIT_STATS")) {
+                if (K.jit_stats) {
                     if (hipMalloc((void**)&h->jit_stats, kJitStatWords * sizeof(unsigned long long)) != hipSuccess) {
                         frt_scene_release(h);
                         return fail("frt_scene_upload: jit stats allocation failed");
@@ -3531,10 +3447,10 @@ int frt_scene_upload(const frt_scene* sc, int device, frt_scene_handle** out) {
                     h->owned.push_back(h->jit_stats);
                     hip_ignore(hipMemset(h->jit_stats, 0, kJitStatWords * sizeof(unsigned long long)));
                 }
-            } else if (std::getenv("FRT_JIT_VERBOSE")) {
+            } else if (K.jit_verbose) {
                 std::fprintf(stderr, "frt: generic shadow walk (%s)\n", why.c_str());
             }
-            if (std::getenv("FRT_JIT_DUMP") && !src.empty()) std::fprintf(stderr, "%s\n", src.c_str());
+            if (K.jit_dump && !src.empty()) std::fprintf(stderr, "%s\n", src.c_str());
         }
     }
     {
@@ -3586,10 +3502,7 @@ int frt_scene_upload(const frt_scene* sc, int device, frt_scene_handle** out) {
             }
         }
     }
-    {
-        const char* wf = std::getenv("FRT_WALK_FLAGS");  // A/B experiments only
-        S.walk_flags = wf ? std::atoi(wf) : 0;
-    }
+    S.walk_flags = K.walk_flags;  // (A/B experiments only)
     S.num_nodes = sc->num_nodes;
     S.num_roots = sc->num_roots;
     S.num_lights = sc->num_lights;
@@ -3597,30 +3510,11 @@ int frt_scene_upload(const frt_scene* sc, int device, frt_scene_handle** out) {
     S.cam = sc->camera;
     S.cfg = sc->config;
     h->host_lights.assign(sc->lights, sc->lights + sc->num_lights);
-    {  // the lit list in row order for the first multi-row area / circle light (FRT_SHADE_SORT=0: never)
-        const char* e = std::getenv("FRT_SHADE_SORT");
-        h->sort_light = -1;
-        for (int l = 0; l < sc->num_lights && h->sort_light < 0 && !(e && std::atoi(e) == 0); ++l)
-            if (sc->lights[l].rows > 1 && sc->lights[l].num_samples > 0) h->sort_light = l;
-        // the row-ordered shading (FRT_SHADE_STAGE): 2 (default) the node records read in row order, the triples
-        // written in row order (spos); 1 also the records staged in list order first (k_lit_stage); 0 both by node, as
-        // round 5 did. Shipped frame: shade 14.2 / 13.1 / 12.9 ms for 0 / 1 / 2 (profiles/r06_ab_shipped_modes.txt)
-        const char* se = std::getenv("FRT_SHADE_STAGE");
-        h->shade_stage = h->sort_light >= 0 ? (se ? std::atoi(se) : 2) : 0;
-        // the secondary levels' queues read in parent order (reflected children, then refracted): appended to
-        // segment blockIdx % kQueueSegs, the segments' order put children of pixels 256 apart side by side, and the
-        // shadow pass's tiles of consecutive nodes spread over the scene. FRT_QUEUE_SORT: 2 (default) the children
-        // at fixed slots (no queue atomics) compacted in order; 1 the segments' entries radix-sorted by parent;
-        // 0 the segments' order (A/B runs, profiles/r06_ab_queue_sort.txt)
-        const char* qs = std::getenv("FRT_QUEUE_SORT");
-        h->queue_sort = qs ? std::atoi(qs) : 2;
-        const char* qsh = std::getenv("FRT_QUEUE_SORT_SHIFT");  // (A/B runs: parents' low bits out of the key)
-        h->queue_sort_shift = qsh ? std::max(0, std::min(16, std::atoi(qsh))) : 0;
-        // k_prepare: a wave whose lanes all hit one leaf reads that leaf's node, transforms and material through the
-        // scalar cache (frt_shade.hpp uniform_view). FRT_PREPARE_UNIFORM=0: every wave per lane (A/B runs, tests)
-        const char* pu = std::getenv("FRT_PREPARE_UNIFORM");
-        h->prepare_uniform = pu && std::atoi(pu) == 0 ? 0 : 1;
-    }
+    // the lit list in row order for the first multi-row area / circle light, and its row-ordered shading
+    h->sort_light = -1;
+    for (int l = 0; l < sc->num_lights && h->sort_light < 0 && K.shade_sort; ++l)
+        if (sc->lights[l].rows > 1 && sc->lights[l].num_samples > 0) h->sort_light = l;
+    h->shade_stage = h->sort_light >= 0 ? K.shade_stage : 0;
     // path-node keys carry a 12-bit heap code (k_prepare: children 2c, 2c + 1 of code c, root 1) and
     // the per-segment counter lines hold the level queue counts in words 0..15: a path of length L
     // has codes up to 2^(L+1) - 1, so L <= 11. The reference accepts any length; deeper recursion
@@ -3657,7 +3551,6 @@ int frt_scene_upload(const frt_scene* sc, int device, frt_scene_handle** out) {
         return fail("frt_scene_upload: debug counters");
     }
 #endif
-    static const bool wtrace = std::getenv("FRT_WARMUP_TRACE") != nullptr;
     const auto ts0 = std::chrono::steady_clock::now();
     {
         std::lock_guard<std::mutex> lk(g_warm_mu);
@@ -3667,7 +3560,7 @@ int frt_scene_upload(const frt_scene* sc, int device, frt_scene_handle** out) {
         }
     }
     const bool stream_ok = h->stream != nullptr || hipStreamCreate(&h->stream) == hipSuccess;
-    if (wtrace)
+    if (K.warmup_trace)
         std::fprintf(stderr, "frt upload: hipStreamCreate %.2f ms\n",
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts0).count());
     if (!stream_ok || hipMalloc((void**)&h->counters, frt::kQueueSegs * frt::kCounterLine * sizeof(unsigned long long)) != hipSuccess ||
@@ -3796,24 +3689,21 @@ void frt_scene_release(frt_scene_handle* h) {
 }
 
 // level 0 leaves eyev to camera_eyev (NodeCols::eye_cam) without GI, and never in a strip of views, whose shading
-// kernels then need no camera at all (FRT_EYE_CAM=0: level 0 stores eyev too, A/B runs)
+// kernels then need no camera at all (fk.eye_cam off: level 0 stores eyev too, A/B runs)
 static int32_t level_eye_cam(const frt_scene_handle* h, size_t d) {
-    static const bool eye_cam_env = !(std::getenv("FRT_EYE_CAM") && std::atoi(std::getenv("FRT_EYE_CAM")) == 0);
-    return d == 0 && !h->S.cfg.use_gi && eye_cam_env && h->strip_views == 0 ? 1 : 0;
+    return d == 0 && !h->S.cfg.use_gi && h->fk.eye_cam && h->strip_views == 0 ? 1 : 0;
 }
 
 // A level stores its nodes' keys unless they are camera_ray's own, which the readers derive (head_key, camera_key):
 // level 0 of a frame of the handle's camera. Level 0 of a strip of views takes its rays, keys included, from
 // k_view_rays' queue; with GI the gather kernels read a node's key without the batch it belongs to; and with a
 // multi-row light, whose row the key picks in every lane of the per-ray shadow kernel, the stored key is an 8-byte
-// load where the derived one is two 64-bit divisions per lane (shipped frame 56.4 -> 59.3 ms with the derived key,
-// profiles/r08_ab_head_cols.txt; FRT_HEAD_KEY0=0, read per frame: level 0 derives them there too, A/B runs and
-// tests/test_head_cols.py). What is left deriving is nobody's hot path: a single-row light's row is 0.
+// load where the derived one is two 64-bit divisions per lane (fk.head_key0 off: level 0 derives them there too).
+// What is left deriving is nobody's hot path: a single-row light's row is 0.
 static bool level_keyed(const frt_scene_handle* h, size_t d) {
     bool multi = false;
     for (const auto& L : h->host_lights) multi = multi || L.rows > 1;
-    const char* e = std::getenv("FRT_HEAD_KEY0");
-    if (e && std::atoi(e) == 0) multi = false;
+    if (!h->fk.head_key0) multi = false;
     return d > 0 || h->S.cfg.use_gi || h->strip_views > 0 || multi;
 }
 
@@ -3881,17 +3771,11 @@ static hipError_t stream_sync(frt_scene_handle* h) {
     return e;
 }
 
-// shading in two kernels (k_shade lists the nodes with light-point work, k_shade_lit shades them);
-// FRT_SHADE_SPLIT=0: one kernel for every node (A/B runs)
-static bool shade_split() {
-    const char* e = std::getenv("FRT_SHADE_SPLIT");
-    return !(e && std::strcmp(e, "0") == 0);
-}
-// the ambient-only nodes' terms computed by k_combine instead of stored by k_shade: with the split and
-// without GI (whose kernels add to the stored surface triples); FRT_SHADE_LAZY=0 stores them (A/B runs)
+// the ambient-only nodes' terms computed by k_combine instead of stored by k_shade: with the shading split in two
+// kernels (fk.shade_split) and without GI (whose kernels add to the stored surface triples); fk.shade_lazy off
+// stores them (A/B runs)
 static bool shade_lazy(const frt_scene_handle* h) {
-    const char* e = std::getenv("FRT_SHADE_LAZY");
-    return shade_split() && !h->S.cfg.use_gi && !(e && std::strcmp(e, "0") == 0);
+    return h->fk.shade_split && !h->S.cfg.use_gi && h->fk.shade_lazy;
 }
 
 // Kernel timing without host synchronisation: events are recorded around each
@@ -3966,8 +3850,7 @@ static void launch_trace(frt_scene_handle* h, const frt::Batch& B, const frt::Qu
                          frt::HitRec* hits = nullptr, int filter_casts = 0, double* hn12 = nullptr, bool jit = false) {
     if (hits == nullptr) hits = h->hits;
     // the scene-specialised closest hit (frt_jit_trace), its undecided rays to the generic walk (k_trace_redo)
-    static const bool jit_trace_env = !(std::getenv("FRT_JIT_TRACE") && std::atoi(std::getenv("FRT_JIT_TRACE")) == 0);
-    if (jit && h->jit_trace && jit_trace_env && !filter_casts && hn12 == nullptr && n > 0 && n < ((int64_t)1 << 31)) {
+    if (jit && h->jit_trace && h->fk.jit_trace && !filter_casts && hn12 == nullptr && n > 0 && n < ((int64_t)1 << 31)) {
         if (!grow(&h->tredo, h->tredo_cap, n + 2)) {  // (a list of every ray at worst, then its counter)
             unsigned cap = (unsigned)(h->tredo_cap - 2);
             unsigned* cnt = (unsigned*)(h->tredo + cap);
@@ -3981,19 +3864,18 @@ static void launch_trace(frt_scene_handle* h, const frt::Batch& B, const frt::Qu
                 case 2: launch_trace_redo_f<2>(h, B, q, n, hits); break;
                 default: launch_trace_redo_f<3>(h, B, q, n, hits); break;
                 }
-                static const bool trace_stats = std::getenv("FRT_JIT_TRACE_STATS") != nullptr;
-                if (trace_stats) {  // (debug: the undecided share per launch; synchronises)
+                if (h->fk.jit_trace_stats) {  // (debug: the undecided share per launch; synchronises)
                     unsigned c = 0;
                     hip_ignore(hipMemcpyAsync(&c, cnt, sizeof(c), hipMemcpyDeviceToHost, h->stream));
                     hip_ignore(hipStreamSynchronize(h->stream));
                     std::fprintf(stderr, "frt: frt_jit_trace level %d: %lld rays, %u to the generic walk\n", B.level,
                                  (long long)n, c);
-                    // (FRT_JIT_TRACE_DUMP=<path>: the level-0 list of undecided rays, int32 ray indices, for analysis)
-                    const char* dump = std::getenv("FRT_JIT_TRACE_DUMP");
-                    if (dump && B.level == 0 && c > 0) {
+                    // (fk.jit_trace_dump: the level-0 list of undecided rays, int32 ray indices, for analysis)
+                    const std::string& dump = h->fk.jit_trace_dump;
+                    if (!dump.empty() && B.level == 0 && c > 0) {
                         std::vector<int32_t> v(std::min<size_t>(c, cap));
                         hip_ignore(hipMemcpy(v.data(), h->tredo, v.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-                        if (FILE* f = std::fopen(dump, "wb")) {
+                        if (FILE* f = std::fopen(dump.c_str(), "wb")) {
                             std::fwrite(v.data(), sizeof(int32_t), v.size(), f);
                             std::fclose(f);
                         }
@@ -4058,28 +3940,23 @@ static void launch_shadow(frt_scene_handle* h, const frt::Batch& B, const frt::H
         // handed back (non-finite rays, usually none)
         using frt::jit::kMixLine;
         using frt::jit::kMixSegs;
-        int64_t NP = 0;  // parts of frt_jit_part_size() samples per path node (frt_jit_beam)
-        for (const auto& L : h->host_lights) NP += std::max(1, (L.num_samples + frt_jit_part_size() - 1) / frt_jit_part_size());
+        const int PS = h->up.jit_part;
+        int64_t NP = 0;  // parts of PS samples per path node (frt_jit_beam)
+        for (const auto& L : h->host_lights) NP += std::max(1, (L.num_samples + PS - 1) / PS);
         // the pair kernel's lane index is 32-bit: batches of more than 2^31 - 1 (node, part) pairs run
         // as node ranges (the shadow kernels read a node's head words and write its counts only, so a
         // range is the same pass over rec.at(off) and counts + off * lights; ranges start at tile boundaries)
-        // (FRT_JIT_MAX_PAIRS lowers the limit: the tests split small batches this way)
-        const char* mp_env = std::getenv("FRT_JIT_MAX_PAIRS");
-        const long long mp = mp_env ? std::atoll(mp_env) : 0;
-        int64_t kMaxPairs = mp >= 1 && mp < (1ll << 31) ? (int64_t)mp : (int64_t)((1ll << 31) - 1);
+        // (fk.jit_max_pairs lowers the limit: the tests split small batches this way)
+        const int64_t mp = h->fk.jit_max_pairs;
+        int64_t kMaxPairs = mp ? mp : (int64_t)((1ll << 31) - 1);
         // (the sub-part pass after the tile kernel: the per-ray kernel's list holds (node pair) * sub + q in 32 bits)
         // Small levels (the deep bounces: a few thousand nodes) skip the beam stages: each stage's launch is sized
         // on the host from the previous one's counts, a round trip (~15 us plus the idle GPU) that costs more than
-        // walking their rays one by one; the per-ray walk of every pair gives the same counts (FRT_JIT_MIN_PAIRS,
-        // default 2^18 (node, part) pairs)
-        static const int64_t min_pairs = [] {
-            const char* e = std::getenv("FRT_JIT_MIN_PAIRS");
-            return e ? (int64_t)std::atoll(e) : (int64_t)1 << 18;
-        }();
-        const bool beam_on = h->jit_beam_on && n * NP >= min_pairs;
+        // walking their rays one by one; the per-ray walk of every pair gives the same counts (fk.jit_min_pairs)
+        const bool beam_on = h->jit_beam_on && n * NP >= h->fk.jit_min_pairs;
         const bool tiled = beam_on && h->tile > 0 && h->jit_tile && h->jit_list && h->tbox;
         const bool subbed = tiled && h->jit_sub && h->sub > 0 && h->light_psamp2 && h->light_sbox;
-        if (subbed && h->node_beam) {
+        if (subbed && h->up.jit_node_beam) {
             kMaxPairs = std::min<int64_t>(kMaxPairs, (int64_t)(0xFFFFFFFFull / (uint64_t)h->sub));
         } else if (subbed) {
             // (the stages' lists hold tile-level entries, ((tile * NP + part) * sub + q) << log2(tile / subtile) +
@@ -4091,7 +3968,7 @@ static void launch_shadow(frt_scene_handle* h, const frt::Batch& B, const frt::H
             const uint64_t per_tile = ((uint64_t)NP * (uint64_t)h->sub) << stl;
             const int64_t tiled_max = (int64_t)(0xFFFFFFFFull / per_tile) * h->tile * NP;
             kMaxPairs = std::min<int64_t>(std::min<int64_t>(tiled_max, (int64_t)0xFFFFFFFFll),
-                                          mp >= 1 && mp < (1ll << 31) ? (int64_t)mp : INT64_MAX);
+                                          mp ? mp : INT64_MAX);
         }
         if (n * NP > kMaxPairs) {
             int64_t per = std::max<int64_t>(1, kMaxPairs / NP);
@@ -4205,11 +4082,9 @@ static void launch_shadow(frt_scene_handle* h, const frt::Batch& B, const frt::H
                         stream_sync(h) != hipSuccess)
                         return;
                     uint64_t listed_s = 0;
-                    // (FRT_JIT_SUBTILE_DEEP=0: levels past the camera's walk the sub-part list ray by ray, A/B runs)
-                    static const bool subtile_deep =
-                        !(std::getenv("FRT_JIT_SUBTILE_DEEP") && std::atoi(std::getenv("FRT_JIT_SUBTILE_DEEP")) == 0);
+                    // (fk.jit_subtile_deep off: levels past the camera's walk the sub-part list ray by ray, A/B runs)
                     const bool subtiled = h->jit_subtile && h->subtile > 0 && h->subtile < h->tile && h->stbox &&
-                                          (B.level == 0 || subtile_deep);
+                                          (B.level == 0 || h->fk.jit_subtile_deep);
                     const uint64_t nst = subtiled ? (uint64_t)(h->tile / h->subtile) : 0;
                     list_blocks = seg_table(h->host_mcount, ssegcap, subtiled ? nst : (uint64_t)h->tile, tseg, listed_s);
                     h->sub_pairs += listed * (uint64_t)h->sub;
@@ -4278,7 +4153,7 @@ static void launch_shadow(frt_scene_handle* h, const frt::Batch& B, const frt::H
                     listed = 0;
                 }
             }
-            if (subbed && !h->node_beam && list_in != h->tlist) {
+            if (subbed && !h->up.jit_node_beam && list_in != h->tlist) {
                 // the sub-part (sub-tile) stage's list goes to the per-ray kernel as it is (host_mcount holds its
                 // counts): each entry's nodes times its sub-part's samples, one lane per (node, sample)
                 direct_in = list_in;
@@ -4360,10 +4235,10 @@ static void launch_shadow(frt_scene_handle* h, const frt::Batch& B, const frt::H
             total_mixed = (uint64_t)npairs;  // every pair, in order (frt_jit_shadow's all_pairs)
         }
         uint32_t all_pairs = beam_on ? 0u : 1u;
-        // lanes per pair (a part of frt_jit_part_size() samples, or a sub-part's slot after frt_jit_sub);
+        // lanes per pair (a part of PS samples, or a sub-part's slot after frt_jit_sub);
         // tid / lpp by multiply-shift
         uint32_t subq = direct_in ? direct_subq : subbed ? 1u : 0u;
-        uint32_t lpp = direct_in ? direct_nodes * (uint32_t)h->sub_ps : subbed ? (uint32_t)h->sub_ps : (uint32_t)frt_jit_part_size();
+        uint32_t lpp = direct_in ? direct_nodes * (uint32_t)h->sub_ps : subbed ? (uint32_t)h->sub_ps : (uint32_t)PS;
         const uint32_t* mixed_in = direct_in ? direct_in : h->mixed;
         uint32_t shift = 32;
         while ((1u << (shift - 32)) < lpp) ++shift;  // 32 + ceil(log2 lpp)
@@ -4725,7 +4600,7 @@ static int upload_host_map(const HostPhotonMap& H, void** out_mem, frt::PhotonMa
 }
 
 static int prepare_photon_map(int64_t n, const double* pos, const double* power, const uint8_t* tp,
-                              double irradiance_radius, HostPhotonMap& H) {
+                              double irradiance_radius, const FrameKnobs& K, HostPhotonMap& H) {
     frt::PhotonMapDev& M = H.M;
     M = frt::PhotonMapDev{};
     if (n > ((int64_t)1 << 30)) return fail("photon map too large");
@@ -4749,16 +4624,8 @@ static int prepare_photon_map(int64_t n, const double* pos, const double* power,
         first = false;
     }
     M.count = nr;
-    static const double cell_div = [] {  // FRT_PM_CELL_DIV: cells per radius (A/B experiments only)
-        const char* e = std::getenv("FRT_PM_CELL_DIV");
-        const double v = e ? std::atof(e) : 3.0;
-        return v >= 1.0 && v <= 16.0 ? v : 3.0;
-    }();
-    static const double max_cells = [] {  // FRT_PM_MAX_CELLS_LOG2: the grid's cell budget (A/B experiments only)
-        const char* e = std::getenv("FRT_PM_MAX_CELLS_LOG2");
-        const int v = e ? std::atoi(e) : 0;
-        return v >= 10 && v <= 30 ? std::ldexp(1.0, v) : kMaxGridCells;
-    }();
+    const double cell_div = K.pm_cell_div;  // cells per radius
+    const double max_cells = K.pm_max_cells_log2 ? std::ldexp(1.0, K.pm_max_cells_log2) : kMaxGridCells;
     double cell = (irradiance_radius > 0 ? irradiance_radius : 1.0) / cell_div;
     int64_t dims[3];
     for (;;) {
@@ -4824,10 +4691,10 @@ static int prepare_photon_map(int64_t n, const double* pos, const double* power,
 }
 
 static int make_photon_map(int64_t n, const double* pos, const double* power, const uint8_t* tp,
-                           double irradiance_radius, void** out_mem, frt::PhotonMapDev& M) {
+                           double irradiance_radius, const FrameKnobs& K, void** out_mem, frt::PhotonMapDev& M) {
     *out_mem = nullptr;
     HostPhotonMap H;
-    if (prepare_photon_map(n, pos, power, tp, irradiance_radius, H)) return -1;
+    if (prepare_photon_map(n, pos, power, tp, irradiance_radius, K, H)) return -1;
     return upload_host_map(H, out_mem, M);
 }
 
@@ -4863,7 +4730,7 @@ static int build_photon_map(frt_scene_handle* h, const std::vector<frt::StoredPh
             });
         for (auto& th : pool) th.join();
     }
-    return prepare_photon_map(n, pos.data(), power.data(), tp.data(), h->S.cfg.irradiance_radius, HM);
+    return prepare_photon_map(n, pos.data(), power.data(), tp.data(), h->S.cfg.irradiance_radius, h->fk, HM);
 }
 
 // The photon maps of one (scene, seed) are the same on every device (the counter RNG), so the devices of one
@@ -4887,9 +4754,8 @@ static std::vector<std::pair<std::pair<uint64_t, uint64_t>, std::weak_ptr<Shared
 static int build_photon_maps(frt_scene_handle* h, uint64_t seed) {
     const auto& cfg = h->S.cfg;
     const int want[2] = {cfg.trace_caustic_map, cfg.trace_global_map};
-    const bool timing = std::getenv("FRT_GI_TIMING") != nullptr;  // diagnostics: host-side phase times
-    // FRT_SHARE_PHOTONS=0: every handle traces its own maps (A/B runs)
-    const bool share = !(std::getenv("FRT_SHARE_PHOTONS") && std::atoi(std::getenv("FRT_SHARE_PHOTONS")) == 0);
+    const bool timing = h->fk.gi_timing;     // diagnostics: host-side phase times
+    const bool share = h->fk.share_photons;  // off: every handle traces its own maps (A/B runs)
     std::shared_ptr<SharedMaps> sm;
     bool producer = true;
     if (share) {
@@ -4989,15 +4855,8 @@ static int shade_gi(frt_scene_handle* h, const frt::Batch& B, frt_scene_handle::
     const int64_t rays_per = (int64_t)cfg.gi_usteps * (int64_t)cfg.gi_vsteps;
     const bool gather = cfg.include_final_gather && rays_per > 0;
     if (gather) {
-        // gather rays per chunk (FRT_GATHER_CHUNK): each chunk's estimate launch ends in a tail of its slowest queries;
-        // 2^22 / 2^24 / 2^25 rays gave 29.33 / 28.97 / 28.92 s GI frames (profiles/r05_ab_gi_chunk.txt); 2^24 keeps
-        // the chunk's buffers at 3.2 GB
-        static const int64_t kChunkRays = [] {
-            const char* e = std::getenv("FRT_GATHER_CHUNK");
-            const long long v = e ? std::atoll(e) : 0;
-            return v >= 1024 ? (int64_t)v : (int64_t)1 << 24;
-        }();
-        const int64_t chunk = std::max<int64_t>(1, kChunkRays / rays_per);
+        // gather rays per chunk (fk.gather_chunk): each chunk's estimate launch ends in a tail of its slowest queries
+        const int64_t chunk = std::max<int64_t>(1, h->fk.gather_chunk / rays_per);
         for (int64_t n0 = 0; n0 < n; n0 += chunk) {
             const int64_t m = std::min(chunk, n - n0);
             const int64_t rays = m * rays_per;
@@ -5009,18 +4868,13 @@ static int shade_gi(frt_scene_handle* h, const frt::Batch& B, frt_scene_handle::
             frt::Batch Bg = B;  // the gather rays form one contiguous queue
             Bg.qprefix = nullptr;
             Bg.qperm = nullptr;
-            // the hemisphere rays through the scene-specialised closest hit where the scene has one (1387 -> 1363 ms per
-            // cornell_gi_480x270_8x8 frame, profiles/r06_ab_gather_jit.txt; round 4's slower kernel lost there,
-            // profiles/r04_ab_gi_trace.txt); FRT_GATHER_JIT=0: the generic walk (A/B runs)
-            // (read per chunk, like the knobs below: a test switches them between frames of one process)
-            const bool gather_jit = !(std::getenv("FRT_GATHER_JIT") && std::atoi(std::getenv("FRT_GATHER_JIT")) == 0);
-            launch_trace(h, Bg, G.gq, rays, G.ghits, 0, nullptr, gather_jit);
-            // FRT_GATHER_QUEUE=0: the static request ranges (A/B runs)
-            const char* qenv = std::getenv("FRT_GATHER_QUEUE");
-            const bool queue = !(qenv && std::strcmp(qenv, "0") == 0) && rays < (int64_t)0xF0000000u;
-            // the requests in the spatial order of their points from 4096 of them (FRT_GATHER_SORT=0: gather order,
-            // =1: sorted at any count)
-            const int sort_mode = std::getenv("FRT_GATHER_SORT") ? std::atoi(std::getenv("FRT_GATHER_SORT")) : -1;
+            // the hemisphere rays through the scene-specialised closest hit where the scene has one (fk.gather_jit)
+            launch_trace(h, Bg, G.gq, rays, G.ghits, 0, nullptr, h->fk.gather_jit);
+            // (fk.gather_queue off: the static request ranges, A/B runs)
+            const bool queue = h->fk.gather_queue && rays < (int64_t)0xF0000000u;
+            // the requests in the spatial order of their points from 4096 of them (fk.gather_sort 0: gather order,
+            // 1: sorted at any count)
+            const int sort_mode = h->fk.gather_sort;
             const bool sorted = queue && sort_mode != 0 && (rays >= 4096 || sort_mode == 1) && rays < (int64_t)0x7FFFFFFF;
             if (sorted && grow(&G.gkeys, G.gkeys_cap, 4 * rays)) return -1;
             uint32_t *k0 = G.gkeys, *k1 = G.gkeys + rays, *i0 = G.gkeys + 2 * rays, *i1 = G.gkeys + 3 * rays;
@@ -5113,23 +4967,23 @@ static void dump_walk_stats(frt_scene_handle* h) {
 
 static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* dev_out, frt_frame_stats* st);
 
-// The frame's shading precision: the params' when they name one, else FRT_PRECISION (read per frame), else parity.
+// The frame's shading precision: the params' when they name one, else FRT_PRECISION (fk.precision), else parity.
 // Sets h->fast32. An unknown value is refused, and so is a fast frame with the shading split off (FRT_SHADE_SPLIT=0
 // shades every node in k_shade, which has no binary32 form): nothing renders parity under the name of fast32.
 static int frame_precision(frt_scene_handle* h, const frt_frame_params* P) {
     int p = P->precision;
     if (p == FRT_PRECISION_DEFAULT) {
-        const char* e = std::getenv("FRT_PRECISION");
-        if (e == nullptr || *e == '\0' || std::strcmp(e, "parity") == 0)
+        const std::string& e = h->fk.precision;
+        if (e.empty() || e == "parity")
             p = FRT_PRECISION_PARITY;
-        else if (std::strcmp(e, "fast32") == 0)
+        else if (e == "fast32")
             p = FRT_PRECISION_FAST32;
         else
             return fail(std::string("FRT_PRECISION=") + e + " is not supported (parity or fast32)");
     }
     if (p != FRT_PRECISION_PARITY && p != FRT_PRECISION_FAST32)
         return fail("precision " + std::to_string(P->precision) + " is not supported");
-    if (p == FRT_PRECISION_FAST32 && !shade_split())
+    if (p == FRT_PRECISION_FAST32 && !h->fk.shade_split)
         return fail("precision fast32 is not supported with FRT_SHADE_SPLIT=0 (the unsplit k_shade is binary64 only)");
     h->fast32 = p == FRT_PRECISION_FAST32;
     return 0;
@@ -5171,6 +5025,7 @@ static int ensure_light32(frt_scene_handle* h) {
 // a failed frame leaves no half-built state behind: photon maps traced by it (maybe truncated by a
 // store overflow) are not reused by the next frame with the same seed
 static int render_impl(frt_scene_handle* h, const frt_frame_params* P, double* dev_out, frt_frame_stats* st) {
+    h->fk = read_frame_knobs();
     h->cur_st = st;
     h->rays_walked = 0;
     h->pairs_walked = 0;
@@ -5199,6 +5054,12 @@ static int render_strip(frt_scene_handle* h, const frt_camera* cams, int32_t nvi
     return rc;
 }
 
+// render_frame's three blocks with a name of their own, defined after it (the kernel templates they launch are then
+// instantiated, and emitted, in the order they always were)
+static int shade_level(frt_scene_handle* h, const frt::Batch& B, int d, int64_t n, frt_frame_stats* st);
+static int64_t close_level(frt_scene_handle* h, const frt::Batch& B, int d, int64_t n, bool dense, frt_frame_stats* st);
+static void frame_stats(frt_scene_handle* h, frt_frame_stats* st, unsigned err);
+
 static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* dev_out, frt_frame_stats* st) {
     using namespace frt;
     FRT_HIP(hipSetDevice(h->device));
@@ -5221,10 +5082,8 @@ static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* 
     // 70 GB of level state, 8 M / 32 M / 128 M samples per batch gave 54.3 / 49.1 / 48.0 ms headline frames,
     // tools/ab_batch.sh). The default suits one-shot calls (render_multi): a handle's first frame allocates its
     // level state, and the driver clears fresh device memory at ~11 GB/s, 6 s for 128 M samples
-    // (tools/rm_batch.py, profiles/r04_ab_batch.txt). FRT_BATCH_SAMPLES overrides the default (A/B runs).
-    const char* benv = std::getenv("FRT_BATCH_SAMPLES");
-    const int64_t bdef = benv && std::atoll(benv) > 0 ? (int64_t)std::atoll(benv) : (int64_t)1 << 23;
-    int64_t batch = P->batch_samples > 0 ? P->batch_samples : bdef;
+    // (tools/rm_batch.py, profiles/r04_ab_batch.txt). fk.batch_samples is that default.
+    int64_t batch = P->batch_samples > 0 ? P->batch_samples : h->fk.batch_samples;
     int64_t pix_per_batch = std::max<int64_t>(1, batch / spp);
     const int path = h->S.cfg.path_length;
     if (st) {
@@ -5336,7 +5195,7 @@ static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* 
                 // the next level dense (FRT_QUEUE_SORT=2, default): child (node, slot) at slot n + node of its queue,
                 // the taken slots compacted in order (reflected children in parent order, then the refracted) into
                 // the next level's qperm, their count into counter word 20 (read back with the queue counts)
-                dense = h->queue_sort == 2 && d < path && 2 * n <= (int64_t)UINT32_MAX && N.cap >= 2 * n;
+                dense = h->up.queue_sort == 2 && d < path && 2 * n <= (int64_t)UINT32_MAX && N.cap >= 2 * n;
                 const int64_t G = (n + 63) >> 6;
                 if (dense && (grow(&h->spawn_masks, h->spawn_masks_cap, 2 * G) ||
                               grow(&h->spawn_offs, h->spawn_offs_cap, 2 * G + 1) || grow(&N.qperm, N.qperm_cap, 2 * n)))
@@ -5345,7 +5204,7 @@ static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* 
                                    dim3(kBlock), 0, h->stream, h->S, B, q, n, h->hits, hn12,
                                    L.rec, N.q, h->counters, h->err, tiles ? h->tbox : nullptr, tl,
                                    subtiles ? h->stbox : nullptr, stl, L.counts, dense ? h->spawn_masks : nullptr,
-                                   h->prepare_uniform);
+                                   h->up.prepare_uniform ? 1 : 0);
                 FRT_HIP(hipGetLastError());
                 if (dense) {
                     hipcub::CountingInputIterator<int64_t> idx(0);
@@ -5386,156 +5245,19 @@ static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* 
                     }
                 }
             }
-            {
-                KTimer t(h, st, 2);
-                const bool split = shade_split();
-                const int64_t nblocks = grid_for(n);
-                const uint32_t segcap = (uint32_t)(((nblocks + kShadeSegs - 1) / kShadeSegs) * kBlock);
-                if (split && (grow(&h->shade_lit, h->shade_lit_cap, (int64_t)segcap * kShadeSegs) ||
-                              grow(&h->shade_lcount, h->shade_lcount_cap, (int64_t)kShadeSegs * jit::kMixLine)))
-                    return -1;
-                if (split)
-                    FRT_HIP(hipMemsetAsync(h->shade_lcount, 0, (size_t)kShadeSegs * jit::kMixLine * sizeof(unsigned),
-                                           h->stream));
-                // the row sort (multi-row light): row counts beside the list, then the list in row order
-                const bool sorted = split && h->sort_light >= 0;
-                const int nrows = sorted ? std::max(1, h->host_lights[(size_t)h->sort_light].rows) : 0;
-                int row_bits = 1;
-                while (row_bits < 32 && (1ll << row_bits) < nrows) ++row_bits;
-                // (the staged records: without GI, whose kernels read and write the surface columns by node)
-                const bool sorted_out = sorted && shade_lazy(h) && L.spos != nullptr && h->shade_stage > 0;
-                const bool staged = sorted_out && h->shade_stage == 1;
-                L.staged = sorted_out;
-                if (sorted) {
-                    const int64_t lcap = (int64_t)segcap * kShadeSegs;
-                    if (grow(&h->lit_row, h->lit_row_cap, 2 * lcap) || grow(&h->lit_flat, h->lit_flat_cap, 2 * lcap))
-                        return -1;
-                    if (staged && grow(&h->lit_stage, h->lit_stage_cap, lcap)) return -1;
-                }
-                if (shade_lazy(h))
-                    hipLaunchKernelGGL(k_shade<true>, dim3(grid_for(n)), dim3(kBlock), 0, h->stream, h->S, B, L.rec, n,
-                                       L.counts, L.surface, h->shade_lit, h->shade_lcount, segcap);
-                else
-                    hipLaunchKernelGGL(k_shade<false>, dim3(grid_for(n)), dim3(kBlock), 0, h->stream, h->S, B, L.rec, n,
-                                       L.counts, L.surface, split ? h->shade_lit : nullptr, h->shade_lcount, segcap);
-                if (sorted) {
-                    KTimer ts(h, st, 16);  // (k_lit_rows + the radix sort, sub_ms["k_lit_sort"])
-                    const int64_t lcap = (int64_t)segcap * kShadeSegs;
-                    uint32_t *keys = h->lit_row, *keys2 = h->lit_row + lcap, *vals = h->lit_flat + lcap;
-                    if (staged)
-                        hipLaunchKernelGGL(k_lit_stage, dim3(grid_for(n)), dim3(kBlock), 0, h->stream, h->S, B, L.rec,
-                                           L.counts, h->shade_lit, h->shade_lcount, segcap, h->sort_light, keys, vals,
-                                           h->lit_stage);
-                    else
-                        hipLaunchKernelGGL(k_lit_rows, dim3(grid_for(n)), dim3(kBlock), 0, h->stream, h->S, B, L.rec.head,
-                                           h->shade_lit, h->shade_lcount, segcap, h->sort_light, keys, vals);
-                    // (the listed count on the host: the sort's size)
-                    auto& lc = h->host_lcount;
-                    FRT_HIP(hipMemcpyAsync(lc.data(), h->shade_lcount, lc.size() * sizeof(unsigned), hipMemcpyDeviceToHost,
-                                           h->stream));
-                    FRT_HIP(stream_sync(h));
-                    int64_t listed = 0;
-                    for (int sgi = 0; sgi < kShadeSegs; ++sgi) listed += lc[(size_t)sgi * jit::kMixLine];
-                    if (st != nullptr) st->lit_nodes += (uint64_t)listed;
-                    if (listed > 0) {
-                        size_t tmp_bytes = 0;
-                        FRT_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, keys2, vals, h->lit_flat,
-                                                                   (int)listed, 0, row_bits, h->stream));
-                        if (grow(&h->scan_tmp, h->scan_tmp_cap, (int64_t)tmp_bytes + 16)) return -1;
-                        FRT_HIP(hipcub::DeviceRadixSort::SortPairs((void*)h->scan_tmp, tmp_bytes, keys, keys2, vals,
-                                                                   h->lit_flat, (int)listed, 0, row_bits, h->stream));
-                    }
-                }
-                if (split && st != nullptr && !sorted) {  // (the stats frame: the listed count, frt_frame_stats.lit_nodes)
-                    auto& lc = h->host_lcount;
-                    FRT_HIP(hipMemcpyAsync(lc.data(), h->shade_lcount, lc.size() * sizeof(unsigned), hipMemcpyDeviceToHost,
-                                           h->stream));
-                    FRT_HIP(hipStreamSynchronize(h->stream));
-                    for (int sgi = 0; sgi < kShadeSegs; ++sgi) st->lit_nodes += lc[(size_t)sgi * jit::kMixLine];
-                }
-#ifndef FRT_SHADE_LIT_BLOCK
-#define FRT_SHADE_LIT_BLOCK 64  // (one wave per block: 9.15 -> 8.83 ms per headline frame, profiles/r05_ab_shade_block.txt; <= kBlock)
-#endif
-                if (split && h->fast32) {
-                    KTimer tl(h, st, 17);  // (inside the shade slot: k_shade_lit32 alone, sub_ms[9])
-                    hipLaunchKernelGGL(sorted ? k_shade_lit32<true> : k_shade_lit32<false>,
-                                       dim3(grid_for(n, FRT_SHADE_LIT_BLOCK)), dim3(FRT_SHADE_LIT_BLOCK), 0, h->stream,
-                                       h->S, B, L.rec, L.counts, L.surface, h->shade_lit, h->shade_lcount, segcap,
-                                       sorted ? (const uint32_t*)h->lit_flat : nullptr,
-                                       staged ? (const frt::LitStage*)h->lit_stage : nullptr,
-                                       sorted_out ? L.spos : nullptr, h->light32);
-                } else if (split) {
-                    KTimer tl(h, st, 15);  // (inside the shade slot: k_shade_lit alone, sub_ms[7])
-                    hipLaunchKernelGGL(sorted ? k_shade_lit<true> : k_shade_lit<false>, dim3(grid_for(n, FRT_SHADE_LIT_BLOCK)),
-                                       dim3(FRT_SHADE_LIT_BLOCK), 0,
-                                       h->stream, h->S, B, L.rec, L.counts, L.surface, h->shade_lit, h->shade_lcount, segcap,
-                                       sorted ? (const uint32_t*)h->lit_flat : nullptr,
-                                       staged ? (const frt::LitStage*)h->lit_stage : nullptr,
-                                       sorted_out ? L.spos : nullptr);
-                }
-                FRT_HIP(hipGetLastError());
-            }
+            if (shade_level(h, B, d, n, st)) return -1;
             if (h->S.cfg.use_gi) {
                 KTimer t(h, st, 7);
                 if (shade_gi(h, B, L, n, st)) return -1;
             }
             if (h->sync_epoch == counters_epoch) FRT_HIP(stream_sync(h));  // (no synchronize since the counters' copy)
-            // the next level's queue segments: prefix counts (a segment past its capacity is an error)
-            int64_t next = 0;
-            bool overflow = false;
-            for (int j = 0; j < kQueueSegs && !dense; ++j) {
-                N.hprefix[j] = next;
-                int64_t c = (int64_t)host_counters[(size_t)j * kCounterLine + d + 1];
-                if (c > B.next_segcap) {
-                    overflow = true;
-                    c = B.next_segcap;
-                }
-                next += c;
-            }
-            if (dense) next = (int64_t)host_counters[20];  // (the compaction's count)
-            N.hprefix[kQueueSegs] = next;
-            if (overflow) {
-                unsigned e = kErrQueueOverflow;
-                FRT_HIP(hipMemcpyAsync(h->err, &e, sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
-            }
-            if (next > 0 && d < path && !dense)
-                FRT_HIP(hipMemcpyAsync(N.qprefix, N.hprefix.data(), (kQueueSegs + 1) * sizeof(int64_t), hipMemcpyHostToDevice,
-                                       h->stream));
-            count[d + 1] = d < path ? next : 0;
-            // the next level in parent order (FRT_QUEUE_SORT): its nodes, tiles and shading then follow the
-            // parents' pixels; keys: refracted bit above the parent index
-            int pbits = 1;
-            while (pbits < 32 && (1ll << pbits) < n) ++pbits;
-            N.sorted = dense || (h->queue_sort == 1 && d < path && next >= 4096 && !overflow && pbits < 32 &&
-                                 N.cap <= (int64_t)UINT32_MAX);
-            if (N.sorted && !dense) {
-                KTimer t(h, st, 6);
-                if (grow(&h->qsort, h->qsort_cap, 3 * next) || grow(&N.qperm, N.qperm_cap, next)) return -1;
-                uint32_t *keys = h->qsort, *keys2 = h->qsort + next, *slots = h->qsort + 2 * next;
-                Batch Bn = B;
-                Bn.qprefix = N.qprefix;
-                Bn.qsegcap = N.cap / kQueueSegs;
-                Bn.qperm = nullptr;
-                const int shift = std::min(h->queue_sort_shift, pbits - 1);
-                hipLaunchKernelGGL(k_queue_keys, dim3(grid_for(next)), dim3(kBlock), 0, h->stream, Bn, N.q, next, pbits,
-                                   shift, keys, slots);
-                FRT_HIP(hipGetLastError());
-                size_t tmp_bytes = 0;
-                FRT_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, keys2, slots, N.qperm, (int)next, 0,
-                                                           pbits - shift + 1, h->stream));
-                if (grow(&h->scan_tmp, h->scan_tmp_cap, (int64_t)tmp_bytes + 16)) return -1;
-                FRT_HIP(hipcub::DeviceRadixSort::SortPairs((void*)h->scan_tmp, tmp_bytes, keys, keys2, slots, N.qperm,
-                                                           (int)next, 0, pbits - shift + 1, h->stream));
-            }
-            if (st) {
-                if (d > 0) st->secondary_rays += (uint64_t)n;
-                else st->primary_rays += (uint64_t)n;
-            }
+            const int64_t next = close_level(h, B, d, n, dense, st);
+            if (next < 0) return -1;
+            count[d + 1] = next;
         }
-        // level 0 combined and resolved in one pass when a block holds whole pixels (FRT_FUSE_RESOLVE=0: the
+        // level 0 combined and resolved in one pass when a block holds whole pixels (fk.fuse_resolve off: the
         // two kernels, A/B runs)
-        const char* fuse_env = std::getenv("FRT_FUSE_RESOLVE");
-        const bool fuse = spp <= kFuseBlock && !(fuse_env && std::strcmp(fuse_env, "0") == 0);
+        const bool fuse = spp <= kFuseBlock && h->fk.fuse_resolve;
         const bool lazy = shade_lazy(h);
         for (int d = path; d >= 0; --d) {
             const int64_t n = count[d];
@@ -5572,48 +5294,7 @@ static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* 
     FRT_HIP(hipMemcpyAsync(&err, h->err, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
     if (st) (void)hipEventRecord(h->ev[1], h->stream);
     FRT_HIP(hipStreamSynchronize(h->stream));
-    if (st) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, h->ev[0], h->ev[1]);
-        st->render_ms = ms;
-        uint64_t pruned = 0, hits = 0, uniform_waves = 0;
-        for (int j = 0; j < kQueueSegs; ++j) {
-            pruned += host_counters[(size_t)j * kCounterLine + 16];
-            hits += host_counters[(size_t)j * kCounterLine + 17];
-            uniform_waves += host_counters[(size_t)j * kCounterLine + 18];
-        }
-        st->prepare_uniform_waves = uniform_waves;
-        st->pruned_secondary = pruned;
-        st->hits = hits;
-        st->shadow_rays = h->S.cfg.include_direct ? hits * (uint64_t)h->samples_per_node : 0;
-        // DESIGN.md byte model of the per-ray shadow kernel: per list entry its 4-byte entry and 4-byte resume word;
-        // per node of an entry its head words (HeadCols: the 24-byte over_point and the 8-byte material word; the 8-byte
-        // key too with a multi-row light, whose row it picks, where the level stores keys: every level but a derived
-        // level 0, counted for all as an upper bound), read once for the entry's rays and at most once per launch for
-        // the node (heads_walked: an entry of the sub-part list holds a tile's 64 nodes, of the node-pair list one),
-        // and one 4-byte count added; with a multi-row light
-        // each ray's 24-byte point from its node's row (a single-row light's points stay in cache); the generic walk:
-        // per shaded node the head words + one 4-byte count per light
-        bool multi = false;
-        for (const auto& L : h->host_lights) multi = multi || L.rows > 1;
-        const double kHead = multi ? 40.0 : 32.0;
-        st->shadow_kernel_bytes = !(h->S.cfg.include_direct && h->samples_per_node > 0) ? 0.0
-                                  : h->jit_shadow != nullptr ? (double)h->pairs_walked * 8.0 + (double)h->heads_walked * (kHead + 4.0) +
-                                                                   (multi ? 24.0 * (double)h->rays_walked : 0.0)
-                                                             : (double)hits * (kHead + 4.0 * h->S.num_lights);
-        st->errors = err;
-        st->shadow_jit = h->jit_shadow != nullptr ? 1 : 0;
-        st->shadow_rays_walked = h->jit_shadow != nullptr ? h->rays_walked : st->shadow_rays;
-        st->shadow_tile_pairs = h->tile_pairs;
-        st->shadow_tile_mixed = h->tile_mixed;
-        st->shadow_pairs = h->node_pairs;
-        st->shadow_pairs_mixed = h->node_mixed;
-        st->shadow_sub_pairs = h->sub_pairs;
-        st->shadow_sub_mixed = h->sub_mixed;
-        st->shadow_subtile_pairs = h->subtile_pairs;
-        st->shadow_subtile_mixed = h->subtile_mixed;
-        collect_timings(h, st);
-    }
+    if (st) frame_stats(h, st, err);
 #if defined(FRT_WALK_STATS) || defined(FRT_WALK_PROF)
     dump_walk_stats(h);
 #endif
@@ -5623,6 +5304,206 @@ static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* 
         return fail(buf);
     }
     return 0;
+}
+
+// A level's shading (timer slot 2): k_shade lists the nodes with light-point work, the row sort puts the list in row
+// order for a multi-row light, and k_shade_lit / k_shade_lit32 shade the listed nodes.
+static int shade_level(frt_scene_handle* h, const frt::Batch& B, int d, int64_t n, frt_frame_stats* st) {
+    using namespace frt;
+    auto& L = h->levels[d];
+    KTimer t(h, st, 2);
+    const bool split = h->fk.shade_split;
+    const int64_t nblocks = grid_for(n);
+    const uint32_t segcap = (uint32_t)(((nblocks + kShadeSegs - 1) / kShadeSegs) * kBlock);
+    if (split && (grow(&h->shade_lit, h->shade_lit_cap, (int64_t)segcap * kShadeSegs) ||
+                  grow(&h->shade_lcount, h->shade_lcount_cap, (int64_t)kShadeSegs * jit::kMixLine)))
+        return -1;
+    if (split)
+        FRT_HIP(hipMemsetAsync(h->shade_lcount, 0, (size_t)kShadeSegs * jit::kMixLine * sizeof(unsigned),
+                               h->stream));
+    // the row sort (multi-row light): row counts beside the list, then the list in row order
+    const bool sorted = split && h->sort_light >= 0;
+    const int nrows = sorted ? std::max(1, h->host_lights[(size_t)h->sort_light].rows) : 0;
+    int row_bits = 1;
+    while (row_bits < 32 && (1ll << row_bits) < nrows) ++row_bits;
+    // (the staged records: without GI, whose kernels read and write the surface columns by node)
+    const bool sorted_out = sorted && shade_lazy(h) && L.spos != nullptr && h->shade_stage > 0;
+    const bool staged = sorted_out && h->shade_stage == 1;
+    L.staged = sorted_out;
+    if (sorted) {
+        const int64_t lcap = (int64_t)segcap * kShadeSegs;
+        if (grow(&h->lit_row, h->lit_row_cap, 2 * lcap) || grow(&h->lit_flat, h->lit_flat_cap, 2 * lcap))
+            return -1;
+        if (staged && grow(&h->lit_stage, h->lit_stage_cap, lcap)) return -1;
+    }
+    if (shade_lazy(h))
+        hipLaunchKernelGGL(k_shade<true>, dim3(grid_for(n)), dim3(kBlock), 0, h->stream, h->S, B, L.rec, n,
+                           L.counts, L.surface, h->shade_lit, h->shade_lcount, segcap);
+    else
+        hipLaunchKernelGGL(k_shade<false>, dim3(grid_for(n)), dim3(kBlock), 0, h->stream, h->S, B, L.rec, n,
+                           L.counts, L.surface, split ? h->shade_lit : nullptr, h->shade_lcount, segcap);
+    if (sorted) {
+        KTimer ts(h, st, 16);  // (k_lit_rows + the radix sort, sub_ms["k_lit_sort"])
+        const int64_t lcap = (int64_t)segcap * kShadeSegs;
+        uint32_t *keys = h->lit_row, *keys2 = h->lit_row + lcap, *vals = h->lit_flat + lcap;
+        if (staged)
+            hipLaunchKernelGGL(k_lit_stage, dim3(grid_for(n)), dim3(kBlock), 0, h->stream, h->S, B, L.rec,
+                               L.counts, h->shade_lit, h->shade_lcount, segcap, h->sort_light, keys, vals,
+                               h->lit_stage);
+        else
+            hipLaunchKernelGGL(k_lit_rows, dim3(grid_for(n)), dim3(kBlock), 0, h->stream, h->S, B, L.rec.head,
+                               h->shade_lit, h->shade_lcount, segcap, h->sort_light, keys, vals);
+        // (the listed count on the host: the sort's size)
+        auto& lc = h->host_lcount;
+        FRT_HIP(hipMemcpyAsync(lc.data(), h->shade_lcount, lc.size() * sizeof(unsigned), hipMemcpyDeviceToHost,
+                               h->stream));
+        FRT_HIP(stream_sync(h));
+        int64_t listed = 0;
+        for (int sgi = 0; sgi < kShadeSegs; ++sgi) listed += lc[(size_t)sgi * jit::kMixLine];
+        if (st != nullptr) st->lit_nodes += (uint64_t)listed;
+        if (listed > 0) {
+            size_t tmp_bytes = 0;
+            FRT_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, keys2, vals, h->lit_flat,
+                                                       (int)listed, 0, row_bits, h->stream));
+            if (grow(&h->scan_tmp, h->scan_tmp_cap, (int64_t)tmp_bytes + 16)) return -1;
+            FRT_HIP(hipcub::DeviceRadixSort::SortPairs((void*)h->scan_tmp, tmp_bytes, keys, keys2, vals,
+                                                       h->lit_flat, (int)listed, 0, row_bits, h->stream));
+        }
+    }
+    if (split && st != nullptr && !sorted) {  // (the stats frame: the listed count, frt_frame_stats.lit_nodes)
+        auto& lc = h->host_lcount;
+        FRT_HIP(hipMemcpyAsync(lc.data(), h->shade_lcount, lc.size() * sizeof(unsigned), hipMemcpyDeviceToHost,
+                               h->stream));
+        FRT_HIP(hipStreamSynchronize(h->stream));
+        for (int sgi = 0; sgi < kShadeSegs; ++sgi) st->lit_nodes += lc[(size_t)sgi * jit::kMixLine];
+    }
+    if (split && h->fast32) {
+        KTimer tl(h, st, 17);  // (inside the shade slot: k_shade_lit32 alone, sub_ms[9])
+        hipLaunchKernelGGL(sorted ? k_shade_lit32<true> : k_shade_lit32<false>,
+                           dim3(grid_for(n, FRT_SHADE_LIT_BLOCK)), dim3(FRT_SHADE_LIT_BLOCK), 0, h->stream,
+                           h->S, B, L.rec, L.counts, L.surface, h->shade_lit, h->shade_lcount, segcap,
+                           sorted ? (const uint32_t*)h->lit_flat : nullptr,
+                           staged ? (const frt::LitStage*)h->lit_stage : nullptr,
+                           sorted_out ? L.spos : nullptr, h->light32);
+    } else if (split) {
+        KTimer tl(h, st, 15);  // (inside the shade slot: k_shade_lit alone, sub_ms[7])
+        hipLaunchKernelGGL(sorted ? k_shade_lit<true> : k_shade_lit<false>, dim3(grid_for(n, FRT_SHADE_LIT_BLOCK)),
+                           dim3(FRT_SHADE_LIT_BLOCK), 0,
+                           h->stream, h->S, B, L.rec, L.counts, L.surface, h->shade_lit, h->shade_lcount, segcap,
+                           sorted ? (const uint32_t*)h->lit_flat : nullptr,
+                           staged ? (const frt::LitStage*)h->lit_stage : nullptr,
+                           sorted_out ? L.spos : nullptr);
+    }
+    FRT_HIP(hipGetLastError());
+    return 0;
+}
+
+// The end of a level: the next level's queue segments from the level's counters (on the host since the level's last
+// synchronize), the overflow flag, the dense count, and the queue in parent order where it is sorted. Returns the next
+// level's node count (0 past the path's last level), negative on an error.
+static int64_t close_level(frt_scene_handle* h, const frt::Batch& B, int d, int64_t n, bool dense, frt_frame_stats* st) {
+    using namespace frt;
+    const int path = h->S.cfg.path_length;
+    const auto& host_counters = h->host_counters;
+    auto& N = h->levels[d + 1];
+    // the next level's queue segments: prefix counts (a segment past its capacity is an error)
+    int64_t next = 0;
+    bool overflow = false;
+    for (int j = 0; j < kQueueSegs && !dense; ++j) {
+        N.hprefix[j] = next;
+        int64_t c = (int64_t)host_counters[(size_t)j * kCounterLine + d + 1];
+        if (c > B.next_segcap) {
+            overflow = true;
+            c = B.next_segcap;
+        }
+        next += c;
+    }
+    if (dense) next = (int64_t)host_counters[20];  // (the compaction's count)
+    N.hprefix[kQueueSegs] = next;
+    if (overflow) {
+        unsigned e = kErrQueueOverflow;
+        FRT_HIP(hipMemcpyAsync(h->err, &e, sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+    }
+    if (next > 0 && d < path && !dense)
+        FRT_HIP(hipMemcpyAsync(N.qprefix, N.hprefix.data(), (kQueueSegs + 1) * sizeof(int64_t), hipMemcpyHostToDevice,
+                               h->stream));
+    // the next level in parent order (FRT_QUEUE_SORT): its nodes, tiles and shading then follow the
+    // parents' pixels; keys: refracted bit above the parent index
+    int pbits = 1;
+    while (pbits < 32 && (1ll << pbits) < n) ++pbits;
+    N.sorted = dense || (h->up.queue_sort == 1 && d < path && next >= 4096 && !overflow && pbits < 32 &&
+                         N.cap <= (int64_t)UINT32_MAX);
+    if (N.sorted && !dense) {
+        KTimer t(h, st, 6);
+        if (grow(&h->qsort, h->qsort_cap, 3 * next) || grow(&N.qperm, N.qperm_cap, next)) return -1;
+        uint32_t *keys = h->qsort, *keys2 = h->qsort + next, *slots = h->qsort + 2 * next;
+        Batch Bn = B;
+        Bn.qprefix = N.qprefix;
+        Bn.qsegcap = N.cap / kQueueSegs;
+        Bn.qperm = nullptr;
+        const int shift = std::min(h->up.queue_sort_shift, pbits - 1);
+        hipLaunchKernelGGL(k_queue_keys, dim3(grid_for(next)), dim3(kBlock), 0, h->stream, Bn, N.q, next, pbits,
+                           shift, keys, slots);
+        FRT_HIP(hipGetLastError());
+        size_t tmp_bytes = 0;
+        FRT_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, keys2, slots, N.qperm, (int)next, 0,
+                                                   pbits - shift + 1, h->stream));
+        if (grow(&h->scan_tmp, h->scan_tmp_cap, (int64_t)tmp_bytes + 16)) return -1;
+        FRT_HIP(hipcub::DeviceRadixSort::SortPairs((void*)h->scan_tmp, tmp_bytes, keys, keys2, slots, N.qperm,
+                                                   (int)next, 0, pbits - shift + 1, h->stream));
+    }
+    if (st) {
+        if (d > 0) st->secondary_rays += (uint64_t)n;
+        else st->primary_rays += (uint64_t)n;
+    }
+    return d < path ? next : 0;
+}
+
+// The instrumented frame's statistics, after its final synchronize: the counters' sums, the shadow pass's pair counts
+// and byte model, the kernel timers.
+static void frame_stats(frt_scene_handle* h, frt_frame_stats* st, unsigned err) {
+    using namespace frt;
+    const auto& host_counters = h->host_counters;
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, h->ev[0], h->ev[1]);
+    st->render_ms = ms;
+    uint64_t pruned = 0, hits = 0, uniform_waves = 0;
+    for (int j = 0; j < kQueueSegs; ++j) {
+        pruned += host_counters[(size_t)j * kCounterLine + 16];
+        hits += host_counters[(size_t)j * kCounterLine + 17];
+        uniform_waves += host_counters[(size_t)j * kCounterLine + 18];
+    }
+    st->prepare_uniform_waves = uniform_waves;
+    st->pruned_secondary = pruned;
+    st->hits = hits;
+    st->shadow_rays = h->S.cfg.include_direct ? hits * (uint64_t)h->samples_per_node : 0;
+    // DESIGN.md byte model of the per-ray shadow kernel: per list entry its 4-byte entry and 4-byte resume word;
+    // per node of an entry its head words (HeadCols: the 24-byte over_point and the 8-byte material word; the 8-byte
+    // key too with a multi-row light, whose row it picks, where the level stores keys: every level but a derived
+    // level 0, counted for all as an upper bound), read once for the entry's rays and at most once per launch for
+    // the node (heads_walked: an entry of the sub-part list holds a tile's 64 nodes, of the node-pair list one),
+    // and one 4-byte count added; with a multi-row light
+    // each ray's 24-byte point from its node's row (a single-row light's points stay in cache); the generic walk:
+    // per shaded node the head words + one 4-byte count per light
+    bool multi = false;
+    for (const auto& L : h->host_lights) multi = multi || L.rows > 1;
+    const double kHead = multi ? 40.0 : 32.0;
+    st->shadow_kernel_bytes = !(h->S.cfg.include_direct && h->samples_per_node > 0) ? 0.0
+                              : h->jit_shadow != nullptr ? (double)h->pairs_walked * 8.0 + (double)h->heads_walked * (kHead + 4.0) +
+                                                               (multi ? 24.0 * (double)h->rays_walked : 0.0)
+                                                         : (double)hits * (kHead + 4.0 * h->S.num_lights);
+    st->errors = err;
+    st->shadow_jit = h->jit_shadow != nullptr ? 1 : 0;
+    st->shadow_rays_walked = h->jit_shadow != nullptr ? h->rays_walked : st->shadow_rays;
+    st->shadow_tile_pairs = h->tile_pairs;
+    st->shadow_tile_mixed = h->tile_mixed;
+    st->shadow_pairs = h->node_pairs;
+    st->shadow_pairs_mixed = h->node_mixed;
+    st->shadow_sub_pairs = h->sub_pairs;
+    st->shadow_sub_mixed = h->sub_mixed;
+    st->shadow_subtile_pairs = h->subtile_pairs;
+    st->shadow_subtile_mixed = h->subtile_mixed;
+    collect_timings(h, st);
 }
 
 // what a camera must satisfy before a frame indexes with it (frt_scene_set_camera, frt_render_views*): positive
@@ -5768,7 +5649,8 @@ int frt_pm_estimate(int device, const double* pos, const double* power, const ui
     frt::PhotonMapDev M{};
     double *dq = nullptr, *dirr = nullptr;
     int64_t* dfound = nullptr;
-    int rc = make_photon_map(n, pos, power, theta_phi, radius, &mem, M);
+    // (no handle: the grid knobs of a frame read now)
+    int rc = make_photon_map(n, pos, power, theta_phi, radius, read_frame_knobs(), &mem, M);
     auto run = [&]() -> int {
         FRT_HIP(hipMalloc(&dq, (size_t)nq * 6 * sizeof(double)));
         FRT_HIP(hipMalloc(&dirr, (size_t)nq * 3 * sizeof(double)));

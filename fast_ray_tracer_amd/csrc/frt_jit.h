@@ -6,24 +6,16 @@
 #include <string>
 #include <vector>
 
+#include "frt_knobs.hpp"
+
 namespace frt {
 struct WalkNode;
 }
 struct frt_light;
 
-// the pair kernel (frt_jit_beam) decides a light's samples in parts of this many consecutive samples
-// (FRT_JIT_PART overrides the default, for A/B runs)
-int frt_jit_part_size();
-// the tile pair kernel (frt_jit_tile) decides runs of this many consecutive path nodes at once (a power of two
-// up to 64; 0: off; FRT_JIT_TILE overrides the default 64)
-int frt_jit_tile_size();
-// the sub-tile kernel (frt_jit_subtile, after the sub-part pass) re-decides the tile sub-pairs left mixed for runs of
-// this many of the tile's nodes (a power of two below the tile size; 0: off; FRT_JIT_SUBTILE overrides the default)
-int frt_jit_subtile_size();
-// the sub-part pass (frt_jit_sub, after the tile kernel) splits the parts of the tile pairs left mixed into this many
-// sub-parts (2 ... 32; 0: off; FRT_JIT_SUB overrides the default 16); their sizes, the largest (PS2), and the
-// sub-parts' samples
-int frt_jit_sub_count();
+// The stage sizes are upload knobs (frt_knobs.hpp): PS = jit_part samples per light part of the pair kernels, the tile
+// kernel's jit_tile consecutive path nodes, the sub-part pass's Q = jit_sub sub-parts per part, the sub-tile kernel's
+// jit_subtile nodes. The sub-parts' sizes, the largest (PS2), and the sub-parts' samples:
 std::vector<int> frt_jit_sub_sizes(int c, int Q);
 int frt_jit_sub_ps(int PS, int Q);
 int frt_jit_light_subparts(const frt_light& L, const double* light_points, const std::vector<int32_t>& order, int PS,
@@ -34,7 +26,7 @@ int frt_jit_light_parts(const frt_light& L, const double* light_points, int PS, 
 // HIP source of the shadow kernel for this tree and these lights ("" and `why` set when the scene
 // is not eligible: too many nodes, or a CSG unit with a leaf whose list is unsorted)
 std::string frt_jit_shadow_source(const frt::WalkNode* wn, int num_nodes, const int32_t* roots, int num_roots,
-                                  const frt_light* lights, int num_lights, std::string& why);
+                                  const frt_light* lights, int num_lights, const UploadKnobs& K, std::string& why);
 
 // the kernels of a scene's module (hipFunction_t; tile / list are null when the source has none)
 struct FrtJitFns {
@@ -47,11 +39,11 @@ struct FrtJitFns {
     void* trace = nullptr;   // frt_jit_trace: closest hit per ray (null where the scene has none)
 };
 // compile with hiprtc for `device` (cached per device and source); 0 on success
-int frt_jit_compile(const std::string& src, int device, FrtJitFns& fns, std::string& log);
+int frt_jit_compile(const std::string& src, int device, const UploadKnobs& K, FrtJitFns& fns, std::string& log);
 
 // this thread's last frt_jit_compile: ms to obtain the code object (0 when the process had it; a disk
 // read or a hiprtc compile otherwise) and to load it into the device's module
 void frt_jit_last_phases(double* obtain_ms, double* load_ms);
 
 // compile only (no device needed): 0 on success
-int frt_jit_compile_only(const std::string& src, const std::string& arch, std::string& log);
+int frt_jit_compile_only(const std::string& src, const std::string& arch, const UploadKnobs& K, std::string& log);

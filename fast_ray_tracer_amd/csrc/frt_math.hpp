@@ -129,14 +129,6 @@ __device__ __forceinline__ double rsqrt_shade(double m2) {
     }
     return inv;
 }
-// vector_normalize (linalg.c:141-148) with the approximate reciprocal magnitude
-__device__ __forceinline__ void normalize3_shade(const double* v, double* r) {
-    const double m2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
-    const double inv = rsqrt_shade(m2);
-    r[0] = v[0] * inv;
-    r[1] = v[1] * inv;
-    r[2] = v[2] * inv;
-}
 // 1 / y and a / b (a >= 0)
 __device__ __forceinline__ double recip_shade(double y) {
     if (!FRT_SHADE_FAST) return 1.0 / y;
@@ -157,16 +149,14 @@ __device__ __forceinline__ double div_shade(double a, double b) {
     return q;
 }
 // lighting_microfacet's brdf_factor (renderer.c:952-963): D G / (4 (n.l)(n.e)), G = min(1, gc (n.e), gc (n.l)),
-// gc = 2 (n.h) / (e.h). FRT_SHADE_MERGE (default 1) takes one reciprocal where the reference divides twice: the
+// gc = 2 (n.h) / (e.h), with one reciprocal where the reference divides twice: the
 // three candidates of G scaled by e.h > 0 keep their order, so G (e.h) = min(e.h, 2 (n.h)(n.e), 2 (n.h)(n.l)) and
 // brdf = D min(..) / ((e.h) 4 (n.l)(n.e)) — a few ulps from the two-quotient form, like the estimates above. A lane
 // whose operands leave [2^-600, 2^600] (e.h = 0 among them: the reference's 1 / (e.h) is inf there and G = 1)
-// takes the reference's form with IEEE quotients. (FRT_SHADE_MERGE=0 builds: a reciprocal and a quotient, A/B runs)
-#ifndef FRT_SHADE_MERGE
-#define FRT_SHADE_MERGE 1
-#endif
+// takes the reference's form with IEEE quotients. (A reciprocal and a quotient measured slower, k_shade_lit 8.70 ->
+// 8.87 ms per headline frame, profiles/r06_ab_shade_merge.txt; that form is left to FRT_SHADE_FAST=0 builds.)
 __device__ __forceinline__ double brdf_shade(double D, double ndh, double edh, double ndl, double ned) {
-    if (FRT_SHADE_MERGE && FRT_SHADE_FAST) {
+    if (FRT_SHADE_FAST) {
         const double g2 = 2.0 * ndh;
         const double a = D * fmin(edh, fmin(g2 * ned, g2 * ndl)), b = edh * (4.0 * ndl * ned);
         double q = a * rcp_nr(b);

@@ -27,8 +27,8 @@
 //            4e-5 at Ns = 200, 1e-4 at Ns = 2000 (instead of 1e-4 and 1e-3).
 //   quotient a few ulps
 //
-// A lane takes the binary64 evaluation of a point (point_term64: the arithmetic of shade_node's term(), FRT_SHADE_ALG
-// and FRT_SHADE_FACTOR forms, without the tail skip, on the point c + offset) when
+// A lane takes the binary64 evaluation of a point (point_term64: the arithmetic of shade_node's term(), shared-term
+// vectors and factored sums, without the tail skip, on the point c + offset) when
 //   m2 outside [2^-40, 2^40]          the reciprocal root or m2 r r would leave the normal range (NaN included)
 //   |l.n| < 2^-17                     the sign of l.n decides whether the point contributes at all (renderer.c:931) and
 //                                     the binary32 value is good to 32u = 2^-19: decided in binary64; this also bounds

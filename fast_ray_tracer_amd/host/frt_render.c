@@ -338,10 +338,13 @@ static pthread_mutex_t g_rm_lock = PTHREAD_MUTEX_INITIALIZER;
 extern char **environ;
 
 /*
- * The FRT_* environment, sorted, as one string: the engine reads its knobs (FRT_JIT, FRT_JIT_BEAM, FRT_MESH,
- * FRT_SHADE_SORT, FRT_JIT_NODE_BEAM, FRT_EYE_CAM, the stage sizes, ...) when a scene is uploaded, so kept handles
- * are reused only under the same knobs. The per-call variables (the device list, seed, stats path, this switch)
- * are left out. Returns a malloc'd string (NULL when out of memory: then nothing is reused).
+ * The FRT_* environment, sorted, as one string: the engine reads its upload knobs (FRT_JIT, FRT_JIT_BEAM, FRT_MESH,
+ * FRT_SHADE_SORT, FRT_JIT_NODE_BEAM, the stage sizes, ...; csrc/frt_knobs.hpp UploadKnobs) once when a scene is
+ * uploaded, so kept handles are reused only under the same knobs: a changed one forces a new upload, which reads it.
+ * The engine's frame knobs (FrameKnobs: FRT_PRECISION, FRT_EYE_CAM, FRT_JIT_MIN_PAIRS, ...) are read at every frame
+ * and would not need one; they are hashed all the same, since the whole FRT_* environment is. The per-call variables
+ * (the device list, seed, stats path, this switch) are left out. Returns a malloc'd string (NULL when out of memory:
+ * then nothing is reused).
  */
 static int
 cmp_str(const void *a, const void *b)

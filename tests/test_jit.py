@@ -158,7 +158,9 @@ print("STATS", d["shadow_jit"], d["shadow_tile_pairs"], d["shadow_sub_pairs"])
 
 
 def _render_env_process(name, env, out, want_stderr=False, **kw):
-    """Render in a fresh process (the tile size and sub-part count are read once per process)."""
+    """Render in a fresh process under `env`. (The stage sizes are upload knobs, csrc/frt_knobs.hpp: they follow each
+    upload, and tests/test_knobs.py switches them inside one process; the fresh process here keeps every case apart
+    from the others' environment and cached modules.)"""
     import subprocess
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
