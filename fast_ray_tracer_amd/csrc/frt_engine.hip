@@ -17,6 +17,9 @@
 //                         written into the parent's fixed child slot
 //   k_resolve             per pixel: ordered sum over (v,u) samples, /total,
 //                         (A+D+S)/3
+//   k_feature_resolve     (the features pass, frt_render_features*: level 0's k_trace
+//                         and k_prepare only) per pixel: depth, normal, albedo,
+//                         coverage and the first hit's leaf / material
 //
 // Children write into fixed parent slots and shadow counts are integers, so
 // the image is independent of wave scheduling. Zero-weight secondary rays
@@ -1546,6 +1549,99 @@ __global__ void __launch_bounds__(kResolveBlock) k_resolve(Cols<Tri9> sample_col
     o[f] = v;
 }
 
+// First-hit feature buffers (frt_render_features*): level 0's closest hits and prepared records, per sample, resolved
+// into per-pixel depth / normal / albedo / coverage (geom: 8 doubles, one 64-byte line per pixel) and the first
+// hitting sample's leaf and material (ids: 2 int32). k_combine_resolve's shape: the level's nodes are the batch's
+// samples in sample order, a block takes ppb = kFeatBlock / spp whole pixels, one thread per sample, stages the
+// sample's seven values and its (leaf, material) in LDS, and thread q then owns (pixel q / 8, plane q % 8): it walks
+// the pixel's run in sub-sample order, misses skipped, so the sums' order of additions is fixed, and eight
+// neighbouring lanes store a pixel's line. The means are one IEEE division per (pixel, plane); nothing is divided
+// per sample and nothing is atomic. spp > kFeatBlock: one pixel per block, its samples in chunks of kFeatBlock, the
+// eight owners carrying their running sums across the chunks (the same additions in the same order).
+// A missed sample's record holds core word 0 only (NodeCols::store_miss): its other words are not read.
+constexpr int kFeatBlock = 256;
+__global__ void __launch_bounds__(kFeatBlock) k_feature_resolve(NodeCols rec, const HitRec* __restrict__ hits,
+                                                                int64_t n, int32_t spp, int32_t ppb, int64_t npix,
+                                                                const frt_material* __restrict__ mats,
+                                                                double* __restrict__ geom, int32_t* __restrict__ ids) {
+    __shared__ double stage[7][kFeatBlock + 1];
+    __shared__ int32_t snode[kFeatBlock], smat[kFeatBlock];  // (snode < 0: the sample missed)
+    const int t = threadIdx.x;
+    auto stage_sample = [&](int slot, int64_t i) {
+        static_assert(sizeof(HitRec) == 16, "HitRec is one 16-byte load");
+        const ulonglong2 hw = *reinterpret_cast<const ulonglong2*>(hits + i);
+        const int32_t node = (int32_t)(uint32_t)hw.y;
+        int32_t mat = -1;
+        double v[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (node >= 0) {
+            const uint64_t w0 = rec.core.w[i];
+            mat = (int32_t)(uint32_t)w0;
+            v[0] = __longlong_as_double((long long)hw.x);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) v[1 + k] = __longlong_as_double((long long)rec.core.w[(2 + k) * rec.core.cap + i]);
+            if ((int32_t)(w0 >> 32) & kOwnColors) {  // (NodeColors words 3..5: Kd)
+#pragma unroll
+                for (int k = 0; k < 3; ++k) v[4 + k] = __longlong_as_double((long long)rec.col.w[(3 + k) * rec.col.cap + i]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) v[4 + k] = mats[mat].Kd[k];
+            }
+        }
+#pragma unroll
+        for (int f = 0; f < 7; ++f) stage[f][slot] = v[f];
+        snode[slot] = node;
+        smat[slot] = mat;
+    };
+    // one (pixel, plane) over kc staged samples from slot s0 on: the ordered sum, the hit count, the first hit's pair
+    auto walk_run = [&](int f, int s0, int kc, double& acc, int32_t& cnt, int32_t& fnode, int32_t& fmat) {
+        const double* st = stage[f < 7 ? f : 0] + s0;
+        for (int kk = 0; kk < kc; ++kk) {
+            const int32_t node = snode[s0 + kk];
+            if (node < 0) continue;
+            acc += st[kk];
+            if (cnt == 0) {
+                fnode = node;
+                fmat = smat[s0 + kk];
+            }
+            ++cnt;
+        }
+    };
+    auto store_plane = [&](int64_t p, int f, double acc, int32_t cnt, int32_t fnode, int32_t fmat) {
+        if (geom != nullptr)
+            geom[8 * p + f] = f == 7 ? (double)cnt / (double)spp : cnt > 0 ? acc / (double)cnt : 0.0;
+        if (ids != nullptr && f == 7) {
+            ids[2 * p] = fnode;
+            ids[2 * p + 1] = fmat;
+        }
+    };
+    if (spp <= kFeatBlock) {
+        const int64_t p0 = (int64_t)blockIdx.x * ppb;
+        const int64_t i = p0 * spp + t;
+        if (t < ppb * spp && i < n) stage_sample(t, i);
+        __syncthreads();
+        for (int q = t; q < ppb * 8; q += kFeatBlock) {
+            const int lp = q >> 3, f = q & 7;
+            if (p0 + lp >= npix) continue;
+            double acc = 0.0;
+            int32_t cnt = 0, fnode = -1, fmat = -1;
+            walk_run(f, lp * spp, spp, acc, cnt, fnode, fmat);
+            store_plane(p0 + lp, f, acc, cnt, fnode, fmat);
+        }
+        return;
+    }
+    const int64_t p = blockIdx.x;  // (one pixel per block: the grid is npix blocks)
+    double acc = 0.0;
+    int32_t cnt = 0, fnode = -1, fmat = -1;
+    for (int32_t c0 = 0; c0 < spp; c0 += kFeatBlock) {
+        const int kc = min(kFeatBlock, spp - c0);
+        const int64_t i = p * spp + c0 + t;
+        if (t < kc && i < n) stage_sample(t, i);
+        __syncthreads();
+        if (t < 8) walk_run(t, 0, kc, acc, cnt, fnode, fmat);
+        __syncthreads();
+    }
+    if (t < 8 && p < npix) store_plane(p, t, acc, cnt, fnode, fmat);
+}
 
 }  // namespace frt
 
@@ -2278,6 +2374,11 @@ struct frt_scene_handle {
     int64_t sample_cap = 0;
     double* out_dev = nullptr;
     int64_t out_cap = 0;
+    // the features pass's device buffers behind a host call (frt_render_features_host / frt_render_feature_views_host)
+    double* feat_geom = nullptr;
+    int64_t feat_geom_cap = 0;
+    int32_t* feat_ids = nullptr;
+    int64_t feat_ids_cap = 0;
     // a strip of views (frt_render_views*): the frame's camera table and its level-0 rays (k_view_rays)
     frt_camera* view_cams = nullptr;
     int64_t view_cams_cap = 0;
@@ -3661,6 +3762,8 @@ void frt_scene_release(frt_scene_handle* h) {
     }
     hip_ignore(hipFree(h->sample_col.w));
     hip_ignore(hipFree(h->out_dev));
+    hip_ignore(hipFree(h->feat_geom));
+    hip_ignore(hipFree(h->feat_ids));
     hip_ignore(hipFree(h->view_cams));
     hip_ignore(hipFree(h->view_q));
     hip_ignore(hipFree(h->counters));
@@ -5506,6 +5609,137 @@ static void frame_stats(frt_scene_handle* h, frt_frame_stats* st, unsigned err) 
     collect_timings(h, st);
 }
 
+// The features pass (frt_render_features*, frt_render_feature_views*): level 0 only, over the batches render_frame
+// would make of the same params: the closest hit (launch_trace), prepare_computations (k_prepare with no bounces
+// left, B.remaining = 0, which gates both spawns: no child ray is queued, so level 1 is only the valid queue pointer
+// the kernel's signature asks for), and k_feature_resolve. No shadow pass, shading, GI or combine kernel runs, no
+// photon map is built or looked at (h->gi is untouched: a GI frame after this pass with an unchanged seed still
+// reports photon_pass == 0), and P->precision / count_reference_rays are not read.
+// h->hits is one buffer that every level of a colour frame reuses, which is why the resolve has to run before
+// anything else writes it; here that holds by construction: level 0 is the only level traced, and a batch's resolve
+// is queued on the stream before the next batch's trace.
+static int feature_frame(frt_scene_handle* h, const frt_frame_params* P, const frt_feature_buffers* dev,
+                         frt_frame_stats* st) {
+    using namespace frt;
+    FRT_HIP(hipSetDevice(h->device));
+    const int64_t hs = h->S.cam.hsize;
+    const int64_t stride = P->row_stride > 0 ? P->row_stride : 1;
+    int64_t nrows = 0;
+    for (int64_t r = P->row_begin; r < P->row_end; r += stride) nrows++;
+    const int32_t nviews = h->strip_views;
+    const int64_t npix = nrows * hs * std::max(1, nviews);
+    if (!h->levels.empty()) h->levels[0].rec.eye_cam = level_eye_cam(h, 0);
+    if (!h->levels.empty() && set_level_head(h, 0)) return -1;
+    const int32_t spp = (int32_t)(h->S.cam.usteps * h->S.cam.vsteps);
+    if (spp <= 0) return fail("render: usteps*vsteps must be positive");
+    if (h->levels.size() < 2) return fail("render: the handle has no level state");
+    const int64_t batch = P->batch_samples > 0 ? P->batch_samples : h->fk.batch_samples;
+    const int64_t pix_per_batch = std::max<int64_t>(1, batch / spp);
+    if (st) {
+        std::memset(st, 0, sizeof(*st));
+        (void)hipEventRecord(h->ev[0], h->stream);
+    }
+    FRT_HIP(hipMemsetAsync(h->err, 0, sizeof(unsigned), h->stream));
+    FRT_HIP(hipMemsetAsync(h->counters, 0, frt::kQueueSegs * frt::kCounterLine * sizeof(unsigned long long), h->stream));
+    for (int64_t p0 = 0; p0 < npix; p0 += pix_per_batch) {
+        const int64_t bp = std::min<int64_t>(pix_per_batch, npix - p0);
+        const int64_t ns = bp * spp;
+        if (ensure_level(h, 0, ns)) return -1;
+        if (nviews > 0 && grow(&h->view_q, h->view_q_cap, ns)) return -1;
+        Batch B{};
+        const int64_t first_row = P->row_begin + ((p0 / hs) % std::max<int64_t>(1, nrows)) * stride;
+        B.sample_begin = (first_row * hs + p0 % hs) * spp;
+        B.pixel_begin = p0;
+        B.num_samples = ns;
+        B.row_begin = P->row_begin;
+        B.row_stride = stride;
+        B.seed = P->seed;
+        B.spp = spp;
+        B.stats = st != nullptr ? 1 : 0;
+        B.level = 0;
+        B.remaining = 0;
+        // (the queue k_prepare's signature asks for: nothing is appended to it)
+        if (ensure_level(h, 1, (int64_t)kQueueSegs * 2 * kBlock)) return -1;
+        auto& L = h->levels[0];
+        auto& N = h->levels[1];
+        B.qprefix = nullptr;
+        B.qperm = nullptr;
+        B.qsegcap = L.cap / kQueueSegs;
+        B.next_segcap = N.cap / kQueueSegs;
+        if (grow(&h->hits, h->hits_cap, ns)) return -1;
+        if (!h->S.cfg.all_ni_one && grow(&h->hn12, h->hn12_cap, 2 * ns)) return -1;
+        double* hn12 = h->S.cfg.all_ni_one ? nullptr : h->hn12;
+        const QueuedRay* q = nviews > 0 ? h->view_q : nullptr;
+        {
+            KTimer t(h, st, 5);
+            if (nviews > 0) {
+                hipLaunchKernelGGL(k_view_rays, dim3(grid_for(ns)), dim3(kBlock), 0, h->stream, h->S, B,
+                                   (const frt_camera*)h->view_cams, nviews, nrows * hs, ns, h->view_q, h->err);
+                FRT_HIP(hipGetLastError());
+            }
+            launch_trace(h, B, q, ns, h->hits, 0, hn12, true);
+            FRT_HIP(hipGetLastError());
+        }
+        {
+            KTimer t(h, st, 6);
+            hipLaunchKernelGGL(h->S.num_patterns > 0 ? k_prepare<true> : k_prepare<false>, dim3(grid_for(ns)),
+                               dim3(kBlock), 0, h->stream, h->S, B, q, ns, h->hits, hn12, L.rec, N.q, h->counters,
+                               h->err, (float*)nullptr, 0, (float*)nullptr, 0, (int32_t*)nullptr,
+                               (unsigned long long*)nullptr, h->up.prepare_uniform ? 1 : 0);
+            FRT_HIP(hipGetLastError());
+        }
+        {
+            KTimer t(h, st, 8 + 10);
+            const int32_t ppb = spp <= kFeatBlock ? kFeatBlock / spp : 1;
+            hipLaunchKernelGGL(k_feature_resolve, dim3((unsigned)((bp + ppb - 1) / ppb)), dim3(kFeatBlock), 0,
+                               h->stream, L.rec, (const HitRec*)h->hits, ns, spp, ppb, bp, h->S.materials,
+                               dev->geom ? dev->geom + 8 * p0 : nullptr, dev->ids ? dev->ids + 2 * p0 : nullptr);
+            FRT_HIP(hipGetLastError());
+        }
+    }
+    unsigned err = 0;
+    FRT_HIP(hipMemcpyAsync(&err, h->err, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    if (st) (void)hipEventRecord(h->ev[1], h->stream);
+    FRT_HIP(hipStreamSynchronize(h->stream));
+    if (st) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, h->ev[0], h->ev[1]);
+        st->render_ms = ms;
+        st->primary_rays = (uint64_t)npix * (uint64_t)spp;
+        st->errors = err;
+        collect_timings(h, st);
+    }
+    if (err) {
+        char buf[128];
+        std::snprintf(buf, sizeof(buf), "render: device error bits 0x%x", err);
+        return fail(buf);
+    }
+    return 0;
+}
+
+static int feature_impl(frt_scene_handle* h, const frt_frame_params* P, const frt_feature_buffers* dev,
+                        frt_frame_stats* st) {
+    h->fk = read_frame_knobs();
+    h->cur_st = st;
+    return feature_frame(h, P, dev, st);
+}
+
+// a strip of views through the features pass: render_strip's borrowing of the handle's camera
+static int feature_strip(frt_scene_handle* h, const frt_camera* cams, int32_t nviews, const frt_frame_params* P,
+                         const frt_feature_buffers* dev, frt_frame_stats* st) {
+    FRT_HIP(hipSetDevice(h->device));
+    if (grow(&h->view_cams, h->view_cams_cap, nviews)) return -1;
+    FRT_HIP(hipMemcpy(h->view_cams, cams, (size_t)nviews * sizeof(frt_camera), hipMemcpyHostToDevice));
+    const frt_camera own = h->S.cam;
+    h->S.cam = cams[0];
+    h->strip_views = nviews;
+    const int rc = feature_impl(h, P, dev, st);
+    h->strip_views = 0;
+    h->S.cam = own;
+    if (!h->levels.empty()) h->levels[0].rec.eye_cam = level_eye_cam(h, 0);
+    return rc;
+}
+
 // what a camera must satisfy before a frame indexes with it (frt_scene_set_camera, frt_render_views*): positive
 // sizes and steps, a sample count per pixel the batches hold in 32 bits, and a sample count per frame whose path-node
 // keys (global sample << 12 | heap code, frt_camera.hpp camera_ray) fit 64 bits
@@ -5624,6 +5858,66 @@ int frt_render_rows(frt_scene_handle* h, const frt_frame_params* P, double* host
     if (rc) return rc;
     FRT_HIP(hipMemcpy(host_rgba, h->out_dev, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
+}
+
+size_t frt_feature_geom_words(void) { return 8; }
+
+// the features pass into the handle's own device buffers, then to the host's (either of which may be NULL)
+static int features_to_host(frt_scene_handle* h, const frt_camera* cams, int32_t nviews, const frt_frame_params* P,
+                            const frt_feature_buffers* host, frt_frame_stats* st) {
+    FRT_HIP(hipSetDevice(h->device));
+    const int64_t stride = P->row_stride > 0 ? P->row_stride : 1;
+    int64_t nrows = 0;
+    for (int64_t r = P->row_begin; r < P->row_end; r += stride) nrows++;
+    const int64_t npix = (int64_t)std::max(1, nviews) * nrows * (cams ? cams[0].hsize : h->S.cam.hsize);
+    frt_feature_buffers dev{nullptr, nullptr};
+    if (host->geom) {
+        if (grow(&h->feat_geom, h->feat_geom_cap, std::max<int64_t>(8 * npix, 8))) return -1;
+        dev.geom = h->feat_geom;
+    }
+    if (host->ids) {
+        if (grow(&h->feat_ids, h->feat_ids_cap, std::max<int64_t>(2 * npix, 2))) return -1;
+        dev.ids = h->feat_ids;
+    }
+    const int rc = cams ? feature_strip(h, cams, nviews, P, &dev, st) : feature_impl(h, P, &dev, st);
+    if (rc) return rc;
+    if (host->geom) FRT_HIP(hipMemcpy(host->geom, dev.geom, (size_t)npix * 8 * sizeof(double), hipMemcpyDeviceToHost));
+    if (host->ids) FRT_HIP(hipMemcpy(host->ids, dev.ids, (size_t)npix * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+static int check_feature_args(const char* who, const void* h, const void* P, const frt_feature_buffers* b) {
+    if (!h || !P || !b) return fail(std::string(who) + ": null argument");
+    if (!b->geom && !b->ids) return fail(std::string(who) + ": both feature buffers are NULL (geom or ids must be given)");
+    return 0;
+}
+
+int frt_render_features_device(frt_scene_handle* h, const frt_frame_params* P, const frt_feature_buffers* dev,
+                               frt_frame_stats* st) {
+    if (check_feature_args("frt_render_features_device", h, P, dev)) return -1;
+    return feature_impl(h, P, dev, st);
+}
+
+int frt_render_features_host(frt_scene_handle* h, const frt_frame_params* P, const frt_feature_buffers* host,
+                             frt_frame_stats* st) {
+    if (check_feature_args("frt_render_features_host", h, P, host)) return -1;
+    return features_to_host(h, nullptr, 0, P, host, st);
+}
+
+int frt_render_feature_views_device(frt_scene_handle* h, const frt_camera* cams, int32_t nviews,
+                                    const frt_frame_params* P, const frt_feature_buffers* dev, frt_frame_stats* st) {
+    if (check_feature_args("frt_render_feature_views_device", h, P, dev)) return -1;
+    if (!cams) return fail("frt_render_feature_views_device: null argument");
+    if (check_views("frt_render_feature_views_device", h, cams, nviews)) return -1;
+    return feature_strip(h, cams, nviews, P, dev, st);
+}
+
+int frt_render_feature_views_host(frt_scene_handle* h, const frt_camera* cams, int32_t nviews,
+                                  const frt_frame_params* P, const frt_feature_buffers* host, frt_frame_stats* st) {
+    if (check_feature_args("frt_render_feature_views_host", h, P, host)) return -1;
+    if (!cams) return fail("frt_render_feature_views_host: null argument");
+    if (check_views("frt_render_feature_views_host", h, cams, nviews)) return -1;
+    return features_to_host(h, cams, nviews, P, host, st);
 }
 
 // photon map test entry points (include/frt_device.h)

@@ -52,7 +52,7 @@ class FrameStats(ctypes.Structure):
     def as_dict(self) -> dict:
         names = ["trace", "shadow", "shade", "combine", "resolve", "trace_primary", "prepare", "gi"]
         subs = ["frt_jit_beam", "frt_jit_shadow", "k_gather_est", "k_gather_hit", "frt_jit_tile", "frt_jit_sub",
-                "frt_jit_subtile", "k_shade_lit", "k_lit_sort", "k_shade_lit32"]
+                "frt_jit_subtile", "k_shade_lit", "k_lit_sort", "k_shade_lit32", "k_feature_resolve"]
         return {
             "primary_rays": int(self.primary_rays), "secondary_rays": int(self.secondary_rays),
             "shadow_rays": int(self.shadow_rays), "pruned_secondary": int(self.pruned_secondary),
@@ -73,6 +73,20 @@ class FrameStats(ctypes.Structure):
             "shadow_subtile_mixed": int(self.shadow_subtile_mixed), "lit_nodes": int(self.lit_nodes),
             "prepare_uniform_waves": int(self.prepare_uniform_waves),
         }
+
+
+class FeatureBuffers(ctypes.Structure):
+    """frt_feature_buffers (include/frt_device.h): either pointer may be null, not both."""
+    _fields_ = [("geom", ctypes.c_void_p), ("ids", ctypes.c_void_p)]
+
+
+FEATURE_GEOM_WORDS = 8  # doubles per pixel of FeatureBuffers.geom (frt_feature_geom_words)
+
+
+def _feature_dict(geom: np.ndarray, ids: np.ndarray) -> dict:
+    """The named planes of the two feature buffers (..., 8) float64 / (..., 2) int32, as views into them."""
+    return {"depth": geom[..., 0], "normal": geom[..., 1:4], "albedo": geom[..., 4:7], "coverage": geom[..., 7],
+            "node": ids[..., 0], "material": ids[..., 1]}
 
 
 class EncodeStats(ctypes.Structure):
@@ -171,6 +185,17 @@ def host_lib(auto_build: bool = False) -> ctypes.CDLL:
         if lib.frt_frame_params_size() != ctypes.sizeof(FrameParams):
             raise RuntimeError("frt: frt_frame_params is %d bytes in %s, runtime.py FrameParams %d: rebuild"
                                % (lib.frt_frame_params_size(), build.DEVICE_LIB, ctypes.sizeof(FrameParams)))
+        lib.frt_feature_geom_words.restype = ctypes.c_size_t
+        if lib.frt_feature_geom_words() != FEATURE_GEOM_WORDS:
+            raise RuntimeError("frt: frt_feature_buffers.geom has %d doubles per pixel in %s, runtime.py %d: rebuild"
+                               % (lib.frt_feature_geom_words(), build.DEVICE_LIB, FEATURE_GEOM_WORDS))
+        fb, fp, fs = ctypes.POINTER(FeatureBuffers), ctypes.POINTER(FrameParams), ctypes.POINTER(FrameStats)
+        for fn in ("frt_render_features_device", "frt_render_features_host"):
+            getattr(lib, fn).restype = ctypes.c_int
+            getattr(lib, fn).argtypes = [vp, fp, fb, fs]
+        for fn in ("frt_render_feature_views_device", "frt_render_feature_views_host"):
+            getattr(lib, fn).restype = ctypes.c_int
+            getattr(lib, fn).argtypes = [vp, vp, ctypes.c_int32, fp, fb, fs]
         _host = lib
         return lib
 
@@ -293,28 +318,20 @@ class GpuRenderer:
             raise RuntimeError("frt: set_camera failed: " + self.lib.frt_host_last_error().decode())
         self.frame = view
 
-    def render_views(self, views, row_begin: int = 0, row_end: int | None = None, row_stride: int = 1,
-                     seed: int = 0x5EED, batch_samples: int = 0, stats: bool = False, precision: str | None = None):
-        """Render K views of this renderer's world in one frame, a strip (frt_render_views_host): an array
-        (K, rows, width, 4) float64 in ordinary pageable memory, view k bit for bit what set_camera(views[k])
-        followed by render(...) with the same arguments gives. The views share their size, steps and jitter; the row
-        range and stride apply inside each view. The levels' launches and count read-backs are paid once for the
-        strip, not once per view. The renderer's own camera is unchanged afterwards."""
+    def _strip_cams(self, who: str, views, allow_empty: bool = False):
+        """The views of a strip as a list and as the flattened frt_camera table the engine takes."""
         views = list(views)
-        if not views:
-            raise ValueError("frt: render_views needs at least one view")
+        if not views and not allow_empty:
+            raise ValueError("frt: %s needs at least one view" % who)
         if any(v.world != self.scene.world for v in views):
-            raise ValueError("frt: render_views needs views of this renderer's world (Scene.view / Scene.view_of)")
+            raise ValueError("frt: %s needs views of this renderer's world (Scene.view / Scene.view_of)" % who)
         lib = self.lib
         lib.frt_camera_size.restype = ctypes.c_size_t
         lib.frt_flatten_camera.restype = ctypes.c_int
         lib.frt_flatten_camera.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_bool,
                                            ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
-        lib.frt_render_views_host.restype = ctypes.c_int
-        lib.frt_render_views_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-                                              ctypes.POINTER(FrameParams), ctypes.c_void_p, ctypes.POINTER(FrameStats)]
         size = lib.frt_camera_size()
-        cams = ctypes.create_string_buffer(size * len(views))
+        cams = ctypes.create_string_buffer(size * max(1, len(views)))
         for k, v in enumerate(views):
             table = ctypes.c_void_p()
             rc = lib.frt_flatten_camera(v.camera, v.usteps, v.vsteps, v.jitter, ctypes.addressof(cams) + k * size,
@@ -322,6 +339,20 @@ class GpuRenderer:
             lib.frt_camera_free(table)  # (free(): the strip uses the handle's table)
             if rc:
                 raise RuntimeError("frt: out of host memory for a view's sample table")
+        return views, cams
+
+    def render_views(self, views, row_begin: int = 0, row_end: int | None = None, row_stride: int = 1,
+                     seed: int = 0x5EED, batch_samples: int = 0, stats: bool = False, precision: str | None = None):
+        """Render K views of this renderer's world in one frame, a strip (frt_render_views_host): an array
+        (K, rows, width, 4) float64 in ordinary pageable memory, view k bit for bit what set_camera(views[k])
+        followed by render(...) with the same arguments gives. The views share their size, steps and jitter; the row
+        range and stride apply inside each view. The levels' launches and count read-backs are paid once for the
+        strip, not once per view. The renderer's own camera is unchanged afterwards."""
+        views, cams = self._strip_cams("render_views", views)
+        lib = self.lib
+        lib.frt_render_views_host.restype = ctypes.c_int
+        lib.frt_render_views_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                              ctypes.POINTER(FrameParams), ctypes.c_void_p, ctypes.POINTER(FrameStats)]
         first, own = views[0], self.frame
         # the handle's sample table is the strip's: a strip of other steps borrows the handle for its first view
         borrow = (first.usteps, first.vsteps) != (own.usteps, own.vsteps)
@@ -396,6 +427,71 @@ class GpuRenderer:
             raise RuntimeError("frt render failed: " + self.lib.frt_last_error().decode())
         return st if stats else None
 
+    def render_features(self, row_begin: int = 0, row_end: int | None = None, row_stride: int = 1,
+                        seed: int = 0x5EED, batch_samples: int = 0, stats: bool = False):
+        """First-hit feature buffers of the rows a render(...) call with the same arguments shades
+        (frt_render_features_host): level 0 only, no shadow, shading or GI work. A dict of numpy arrays: depth
+        (rows, w), normal (rows, w, 3), albedo (rows, w, 3), coverage (rows, w), all float64 and views into one
+        (rows, w, 8) buffer ("geom"), and node, material (rows, w) int32, views into one (rows, w, 2) buffer
+        ("ids"). Each value is the mean over the pixel's hitting samples in sub-sample order (coverage: hits / spp;
+        node / material: the first hitting sample's; -1 and zeros where nothing is hit): include/frt_device.h
+        frt_feature_buffers. scene_nodes() maps a node id back to the flattened tree."""
+        p = self._params(row_begin, row_end, row_stride, seed, batch_samples)
+        n = self.rows_in(p.row_begin, p.row_end, row_stride)
+        geom = np.zeros((n, self.frame.width, FEATURE_GEOM_WORDS), dtype=np.float64)
+        ids = np.zeros((n, self.frame.width, 2), dtype=np.int32)
+        bufs = FeatureBuffers(geom.ctypes.data, ids.ctypes.data)
+        st = FrameStats()
+        rc = self.lib.frt_render_features_host(self.handle, ctypes.byref(p), ctypes.byref(bufs),
+                                               ctypes.byref(st) if stats else None)
+        if rc != 0:
+            raise RuntimeError("frt render_features failed: " + self.lib.frt_last_error().decode())
+        out = _feature_dict(geom, ids)
+        return (out, st) if stats else out
+
+    def render_features_into(self, geom_ptr: int | None, ids_ptr: int | None, row_begin: int = 0,
+                             row_end: int | None = None, row_stride: int = 1, seed: int = 0x5EED,
+                             batch_samples: int = 0, stats: bool = False):
+        """render_features into device memory (frt_render_features_device): geom_ptr rows x w x 8 float64, ids_ptr
+        rows x w x 2 int32 (e.g. torch.cuda tensors' data_ptr()); either may be None, not both."""
+        p = self._params(row_begin, row_end, row_stride, seed, batch_samples)
+        bufs = FeatureBuffers(geom_ptr or None, ids_ptr or None)
+        st = FrameStats()
+        rc = self.lib.frt_render_features_device(self.handle, ctypes.byref(p), ctypes.byref(bufs),
+                                                 ctypes.byref(st) if stats else None)
+        if rc != 0:
+            raise RuntimeError("frt render_features failed: " + self.lib.frt_last_error().decode())
+        return st if stats else None
+
+    def render_feature_views(self, views, row_begin: int = 0, row_end: int | None = None, row_stride: int = 1,
+                             seed: int = 0x5EED, batch_samples: int = 0, stats: bool = False):
+        """render_features of K views of this renderer's world in one pass, a strip (frt_render_feature_views_host):
+        render_features' dict with a leading K axis, view k bit for bit what set_camera(views[k]) followed by
+        render_features(...) with the same arguments gives. The views share their size, steps and jitter, as
+        render_views' do; the renderer's own camera is unchanged afterwards."""
+        views, cams = self._strip_cams("render_feature_views", views, allow_empty=True)  # (none: the engine refuses)
+        first, own = views[0] if views else self.frame, self.frame
+        # the handle's sample table is the strip's: a strip of other steps borrows the handle for its first view
+        borrow = (first.usteps, first.vsteps) != (own.usteps, own.vsteps)
+        if borrow:
+            self.set_camera(first)
+        try:
+            p = self._params(row_begin, first.height if row_end is None else row_end, row_stride, seed, batch_samples)
+            n = self.rows_in(p.row_begin, p.row_end, row_stride)
+            geom = np.zeros((len(views), n, first.width, FEATURE_GEOM_WORDS), dtype=np.float64)
+            ids = np.zeros((len(views), n, first.width, 2), dtype=np.int32)
+            bufs = FeatureBuffers(geom.ctypes.data, ids.ctypes.data)
+            st = FrameStats()
+            rc = self.lib.frt_render_feature_views_host(self.handle, cams, len(views), ctypes.byref(p),
+                                                        ctypes.byref(bufs), ctypes.byref(st) if stats else None)
+            err = self.lib.frt_last_error().decode() if rc != 0 else ""
+        finally:
+            if borrow:
+                self.set_camera(own)
+        if rc != 0:
+            raise RuntimeError("frt render_feature_views failed: " + err)
+        out = _feature_dict(geom, ids)
+        return (out, st) if stats else out
 
     def render_encoded(self, mode: str = "ppm_scaled", **render_args):
         """Render the whole frame into device memory (a torch tensor, frt_render_rows_device) and encode it there
@@ -534,6 +630,27 @@ def _flat_scene(scene: Scene):
     if lib.frt_flatten_scene(scene.camera, scene.world, scene.usteps, scene.vsteps, scene.jitter, fs, err, 512):
         raise RuntimeError("frt: flatten failed: " + err.value.decode())
     return lib, fs
+
+
+# frt_node (include/frt_device.h): 8 int32 and the 6 doubles of its box, 80 bytes
+_NODE_DTYPE = np.dtype([("type", "<i4"), ("skip", "<i4"), ("parent", "<i4"), ("tparent", "<i4"), ("xform", "<i4"),
+                        ("material", "<i4"), ("prim", "<i4"), ("right", "<i4"), ("bbox", "<f8", (6,))])
+
+
+def scene_nodes(scene: Scene) -> dict:
+    """The flattened object tree of a scene (or view) in pre-order, as the device holds it: {"type" (enum
+    frt_node_type: 8 CSG and 9 group are the composites, everything else a leaf), "parent" (-1: a world shape),
+    "material" (index into the flattened materials; leaves)}, int32 arrays of one entry per node. A `node` id of
+    GpuRenderer.render_features indexes them."""
+    lib, fs = _flat_scene(scene)
+    try:
+        num = ctypes.c_int32.from_buffer(fs, 4).value  # frt_scene: abi_version, num_nodes, nodes
+        ptr = ctypes.c_void_p.from_buffer(fs, 8).value
+        nodes = np.frombuffer(ctypes.string_at(ptr, num * _NODE_DTYPE.itemsize), dtype=_NODE_DTYPE) if num > 0 \
+            else np.zeros(0, dtype=_NODE_DTYPE)
+        return {k: np.array(nodes[k], dtype=np.int32) for k in ("type", "parent", "material")}
+    finally:
+        lib.frt_flat_scene_free(fs)
 
 
 def jit_check(scene: Scene) -> tuple[int, str, str]:

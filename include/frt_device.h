@@ -233,7 +233,8 @@ typedef struct frt_frame_stats {
        3 k_gather_hit, 4 frt_jit_tile (tile pair kernel), 5 frt_jit_sub (sub-part pair kernel), 6 frt_jit_subtile
        (sub-tile pair kernel), 7 k_shade_lit (the shading of the path nodes some light reaches; 0 in a fast32 frame), 8 k_lit_scan +
        k_lit_scatter (the lit list in light-row order, multi-row lights), 9 k_shade_lit32 (k_shade_lit's place in a
-       fast32 frame; 0 in a parity frame); 10-15 unused */
+       fast32 frame; 0 in a parity frame), 10 k_feature_resolve (the features pass, frt_render_features*; 0 in a colour
+       frame); 11-15 unused */
     double sub_ms[16];
     uint64_t sub_launches[16];
     uint64_t shadow_rays_walked;  /* shadow rays walked one by one; the rest of shadow_rays were resolved
@@ -313,6 +314,55 @@ int frt_render_views_host(frt_scene_handle *h, const frt_camera *cams, int32_t n
                           double *host_rgba, frt_frame_stats *stats);
 int frt_render_views_device(frt_scene_handle *h, const frt_camera *cams, int32_t nviews,
                             const frt_frame_params *params, double *device_rgba, frt_frame_stats *stats);
+
+/*
+ * First-hit feature buffers: what level 0 knows about each pixel, without shading it. The pass runs the closest hit
+ * and prepare_computations of the camera samples a colour frame with the same params traces (rows, stride, seed,
+ * batch, jitter and aperture alike: sample `sub` of pixel `p` is the same camera_ray in both) and nothing else: no
+ * shadow, shading, GI or combine kernel, and no photon pass. params' precision and count_reference_rays are ignored.
+ * A sample hits when its closest hit has a leaf.
+ *
+ * geom: 8 doubles per pixel (one 64-byte line), pixels in the colour output's order:
+ *   [0]    depth     mean over the hitting samples of the closest hit's t. ray_for_pixel normalises the direction, so
+ *                    t is the Euclidean distance from the ray's origin (with an aperture: the lens point)
+ *   [1..3] normal    mean over the hitting samples of comps.normalv: world space, turned towards the eye when the hit
+ *                    is inside, after a bump map; the mean is not renormalised
+ *   [4..6] albedo    mean over the hitting samples of Kd as prepare_computations leaves it: the pattern's colour
+ *                    where the material has a map_Kd, else the material's Kd
+ *   [7]    coverage  hits / spp (one IEEE division)
+ * Each mean is the sum in sub-sample order (sub = v * usteps + u ascending, misses skipped) divided by the hit count
+ * with one IEEE division; a pixel without a hit holds eight +0.0. The result is a placement, as the colour frame is:
+ * bit-identical for any batch size, row split, strip position or wave schedule.
+ * ids: 2 int32 per pixel: the pre-order node index of the leaf and the material index of the pixel's first hitting
+ * sample in sub-sample order; -1, -1 without a hit.
+ *
+ * Either buffer may be NULL (not both). The *_device calls take device memory on the handle's device, the *_host
+ * calls host memory. The *_views calls render a strip as frt_render_views* does (same rules for the cameras, the
+ * output view-major): view k is, bit for bit, frt_scene_set_camera(cams[k]) + frt_render_features*.
+ * stats (may be NULL) receives primary_rays, render_ms, errors, kernel_ms / kernel_launches [5] (trace) and [6]
+ * (prepare), and sub_ms / sub_launches [10] (k_feature_resolve); everything else is 0.
+ * Returns 0, or -1 with the reason in frt_last_error (a null handle, params or buffers; both buffers NULL; a strip's
+ * refusals; device error bits). The handle is left as a colour frame leaves it: its camera, kernels and photon maps
+ * stay.
+ */
+typedef struct frt_feature_buffers {
+    double *geom;  /* 8 doubles per pixel, or NULL */
+    int32_t *ids;  /* 2 int32 per pixel, or NULL */
+} frt_feature_buffers;
+
+int frt_render_features_device(frt_scene_handle *h, const frt_frame_params *params, const frt_feature_buffers *dev,
+                               frt_frame_stats *stats);
+int frt_render_features_host(frt_scene_handle *h, const frt_frame_params *params, const frt_feature_buffers *host,
+                             frt_frame_stats *stats);
+int frt_render_feature_views_device(frt_scene_handle *h, const frt_camera *cams, int32_t nviews,
+                                    const frt_frame_params *params, const frt_feature_buffers *dev,
+                                    frt_frame_stats *stats);
+int frt_render_feature_views_host(frt_scene_handle *h, const frt_camera *cams, int32_t nviews,
+                                  const frt_frame_params *params, const frt_feature_buffers *host,
+                                  frt_frame_stats *stats);
+
+/* doubles per pixel of frt_feature_buffers.geom (8): a caller's mirror checks it (no device needed) */
+size_t frt_feature_geom_words(void);
 
 void frt_scene_release(frt_scene_handle *h);
 
