@@ -3,6 +3,7 @@
 // frt_jit_trace), which generates its level-0 rays in place as k_trace does.
 #pragma once
 
+#include "frt_cam_index.hpp"
 #include "frt_shadow.hpp"
 
 namespace frt {
@@ -107,16 +108,24 @@ __device__ inline void aperture_point(const frt_camera& cam, uint64_t seed, uint
     xy[1] = 0.5;
 }
 
+// origin0: the origin of a camera without an aperture, computed once per camera (DevScene::cam_origin: this
+// function's own expression at ap = (0.5, 0.5)); null: computed here
 __device__ __forceinline__ void ray_for_pixel(const frt_camera& cam, double px, double py, const double* jit,
-                                              const double* ap, Ray& r) {
+                                              const double* ap, const double* origin0, Ray& r) {
     // renderer.c:95-129; ap = aperture_fn's point in [0,1)^2 (sample_aperture subtracts 0.5, camera.c:85-90)
     double xoff = (px + jit[0]) * cam.pixel_size;
     double yoff = (py + jit[1]) * cam.pixel_size;
     double wx = cam.half_width - xoff, wy = cam.half_height - yoff;
     double p[3] = {wx, wy, -cam.canvas_distance}, pixel[3], origin[3];
     xf_point(cam.inv, p, pixel);
-    double q[3] = {(ap[0] - 0.5) * cam.aperture_size, (ap[1] - 0.5) * cam.aperture_size, 0.0};
-    xf_point(cam.inv, q, origin);
+    if (origin0 != nullptr) {
+        origin[0] = origin0[0];
+        origin[1] = origin0[1];
+        origin[2] = origin0[2];
+    } else {
+        double q[3] = {(ap[0] - 0.5) * cam.aperture_size, (ap[1] - 0.5) * cam.aperture_size, 0.0};
+        xf_point(cam.inv, q, origin);
+    }
     double v[3] = {pixel[0] - origin[0], pixel[1] - origin[1], pixel[2] - origin[2]};
     r.o[0] = origin[0];
     r.o[1] = origin[1];
@@ -127,13 +136,35 @@ __device__ __forceinline__ void ray_for_pixel(const frt_camera& cam, double px, 
 // global sample index of sample s of a batch's level 0: the pixel's index in the whole frame (the batch's rows may be
 // a strided part of it) times spp plus the sub-pixel sample (sub = v * usteps + u). The one place the expression
 // lives: camera_ray and camera_key (the level-0 keys that HeadCols does not store) both take it from here.
+// B.cam_fast (the host's cam_index_fits32): s and the pixel index are 32-bit values, the two quotients multiply-shift
+// (frt_cam_index.hpp), the remainders a multiply-subtract, column and row doubles from 32-bit integers; the products
+// of global_pixel and global_sample stay 64-bit. Otherwise two signed 64-bit divisions. The same integers, and the
+// same doubles, either way.
 struct CameraSample {
     int64_t row, col;
     uint64_t global_pixel, global_sample;
     int sub;
+    double px, py;  // col, row
 };
 __device__ __forceinline__ CameraSample camera_sample(const DevScene& S, const Batch& B, int64_t s) {
     CameraSample c;
+    if (B.cam_fast) {
+        const uint32_t s32 = (uint32_t)s, spp = (uint32_t)B.spp, hs = (uint32_t)S.cam.hsize;
+        const uint32_t sp = magic_div(s32, B.spp_magic, B.spp_shift);
+        const uint32_t sub = magic_rem(s32, sp, spp);
+        const uint32_t pix = (uint32_t)B.pixel_begin + sp;
+        const uint32_t prow = magic_div(pix, B.hs_magic, B.hs_shift);
+        const uint32_t col = magic_rem(pix, prow, hs);
+        const uint32_t row = (uint32_t)B.row_begin + prow * (uint32_t)B.row_stride;
+        c.sub = (int)sub;
+        c.row = (int64_t)row;
+        c.col = (int64_t)col;
+        c.global_pixel = (uint64_t)row * (uint64_t)hs + (uint64_t)col;
+        c.global_sample = c.global_pixel * (uint64_t)spp + (uint64_t)sub;
+        c.px = (double)col;
+        c.py = (double)row;
+        return c;
+    }
     const int64_t pix = B.pixel_begin + s / B.spp;
     c.sub = (int)(s % B.spp);
     const int64_t hs = S.cam.hsize;
@@ -141,6 +172,8 @@ __device__ __forceinline__ CameraSample camera_sample(const DevScene& S, const B
     c.col = pix % hs;
     c.global_pixel = (uint64_t)(c.row * hs + c.col);
     c.global_sample = c.global_pixel * (uint64_t)B.spp + (uint64_t)c.sub;
+    c.px = (double)c.col;
+    c.py = (double)c.row;
     return c;
 }
 
@@ -163,7 +196,8 @@ __device__ __forceinline__ void camera_ray(const DevScene& S, const Batch& B, in
         jit[1] = S.sample_table[2 * sub + 1];
     }
     if (S.cam.aperture_size != 0.0) aperture_point(S.cam, B.seed, c.global_sample, ap, err);
-    ray_for_pixel(S.cam, (double)c.col, (double)c.row, jit, ap, r);
+    // (cam_origin_set only where aperture_size == 0: ap is then the centre the stored origin was computed at)
+    ray_for_pixel(S.cam, c.px, c.py, jit, ap, S.cam_origin_set ? S.cam_origin : nullptr, r);
     key = (c.global_sample << 12) | 1ull;
 }
 

@@ -306,6 +306,11 @@ __global__ void __launch_bounds__(kTraceBlock) k_trace_redo(DevScene S, Batch B,
 #ifndef FRT_PREPARE_WAVES
 #define FRT_PREPARE_WAVES 1
 #endif
+// (1: a node's hit record, and on the uniform path its leaf's first scalar loads, are issued before its ray is made
+// or loaded; 0: after, the order up to round 9, for A/B builds: profiles/r10_ab_camera.txt)
+#ifndef FRT_PREPARE_LOADS_FIRST
+#define FRT_PREPARE_LOADS_FIRST 1
+#endif
 // (one path node; returns whether it has a hit, its over_point in op)
 template <bool kPat>
 __device__ __forceinline__ bool prepare_node(const DevScene& S, const Batch& B, const QueuedRay* __restrict__ q,
@@ -331,6 +336,47 @@ __device__ __forceinline__ bool prepare_node(const DevScene& S, const Batch& B, 
     Ray r;
     uint64_t key;
     int32_t parent = -1, slot = 0;
+#if FRT_PREPARE_LOADS_FIRST
+    // The hit record first: it does not depend on the ray, and the compiler does not move its load across
+    // camera_ray's branches. A level-0 miss is done with it (its record is material -1 alone: no ray, no key). Where
+    // the wave may take the uniform path, the hit leaf's node record and transform chain, the head of the dependent
+    // scalar loads (node, chain, transforms, primitive, material), are asked for before the camera ray is made, whose
+    // arithmetic then runs while they travel; prepare_hit reads the same addresses again, from the scalar cache.
+    // The queued levels load the ray and the hit together. Per lane the operations and their order are as they were.
+    const HitRec hr = hits[node];
+    if (q == nullptr) {
+        if (hr.node < 0) {
+            rec.store_miss(node, parent, slot);  // (material -1: what the shadow pass tests too, HeadCols::hit)
+            return false;
+        }
+        int early_type = 0, early_chain = 0;
+        if (uniform_ok) {
+            const DevScene U = uniform_view(S);
+            const int leaf_e = uniform(hr.node);
+            early_type = U.nodes[leaf_e].type;
+            early_chain = U.xchain[leaf_e].x;
+        }
+        unsigned ce = 0;
+        camera_ray(S, B, node, r, key, ce);
+        // (the early loads' values are waited for here, after the arithmetic, so that they are not dropped as unused)
+        asm volatile("" ::"s"(early_type), "s"(early_chain));
+    } else {
+        const QueuedRay& qr = q[queue_slot(B, node)];
+        for (int k = 0; k < 3; ++k) {
+            r.o[k] = qr.o[k];
+            r.d[k] = qr.d[k];
+        }
+        key = qr.key;
+        parent = qr.parent;
+        slot = qr.slot;
+        if (hr.node < 0) {
+            rec.store_miss(node, parent, slot);
+            return false;
+        }
+    }
+    PSTAMP(0);
+    PSTAMP(1);
+#else
     if (q == nullptr) {
         unsigned ce = 0;
         camera_ray(S, B, node, r, key, ce);
@@ -351,6 +397,7 @@ __device__ __forceinline__ bool prepare_node(const DevScene& S, const Batch& B, 
         rec.store_miss(node, parent, slot);  // (material -1: what the shadow pass tests too, HeadCols::hit)
         return false;
     }
+#endif
     // the rest per hit: on the scene as it is (leaf: the lane's own), or on its uniform view where every lane of the
     // wave hit one leaf (leaf: that leaf, wave-uniform); the same operations in the same order either way
     auto prepare_hit = [&](const DevScene& S, const int leaf) __attribute__((always_inline)) {
@@ -634,10 +681,12 @@ __global__ void __launch_bounds__(kBlock) k_view_rays(DevScene S, Batch B, const
     const int view = (int)min((int64_t)(nviews - 1), pix / view_pixels);
     Batch Bv = B;  // (camera_ray's pixel of sample i: Bv.pixel_begin + i / spp = the pixel inside the view)
     Bv.pixel_begin = pix - (int64_t)view * view_pixels - i / B.spp;
+    Bv.cam_fast = 0;  // (the re-based pixel_begin may be negative; the host leaves a strip's batches at 0 too)
     unsigned e = 0;
     auto emit = [&](const frt_camera& cam) {
         DevScene Sv = S;
         Sv.cam = cam;
+        Sv.cam_origin_set = 0;  // (S.cam_origin is not this view's)
         QueuedRay qr;
         Ray r;
         camera_ray(Sv, Bv, i, r, qr.key, e);
@@ -2383,6 +2432,7 @@ struct frt_scene_handle {
     frt_camera* view_cams = nullptr;
     int64_t view_cams_cap = 0;
     int32_t strip_views = 0;  // views of the frame being rendered (0: a frame of the handle's own camera)
+    bool cam_origin_ok = false;  // S.cam_origin holds S.cam's ray origin (set_scene_camera)
     frt::QueuedRay* view_q = nullptr;
     int64_t view_q_cap = 0;
     // kQueueSegs lines of kCounterLine words: [d] queue segment count of level d, [16] pruned,
@@ -2442,6 +2492,48 @@ static int fail(const std::string& msg) {
         hipError_t e_ = (call);                                                                         \
         if (e_ != hipSuccess) return fail(std::string(#call) + ": " + hipGetErrorString(e_));          \
     } while (0)
+
+// The handle's camera, and with it what every ray of the camera shares: without an aperture the origin is
+// ray_for_pixel's xf_point(cam.inv, q) at q = ((0.5 - 0.5) * aperture_size, the same, 0), the same 18 multiply-adds in
+// every lane of a frame. Computed here once per camera, in frt_math.hpp xf_point's operation order (this file is
+// built with -ffp-contract=off: the binary64 operations the device rounds the same way). A camera whose inverse is
+// not finite keeps the device's own arithmetic (the payload of a NaN is not the host's to predict).
+static void set_scene_camera(frt_scene_handle* h, const frt_camera& cam) {
+    h->S.cam = cam;
+    h->cam_origin_ok = false;
+    if (cam.aperture_size != 0.0) return;
+    const double* m = cam.inv;
+    const double q[3] = {(0.5 - 0.5) * cam.aperture_size, (0.5 - 0.5) * cam.aperture_size, 0.0};
+    bool finite = true;
+    for (int r = 0; r < 3; ++r) {
+        const double v = ((m[4 * r] * q[0] + m[4 * r + 1] * q[1]) + m[4 * r + 2] * q[2]) + m[4 * r + 3];
+        h->S.cam_origin[r] = v;
+        finite = finite && std::isfinite(v);
+    }
+    h->cam_origin_ok = finite;
+}
+
+// FRT_CAM_FAST for the frame about to render: the stored origin where the camera has one (a strip's rays come from
+// its camera table, k_view_rays: the present arithmetic)
+static void frame_camera_consts(frt_scene_handle* h) {
+    h->S.cam_origin_set = h->fk.cam_fast && h->cam_origin_ok && h->strip_views == 0 ? 1 : 0;
+}
+
+// a batch's level-0 index math (frt_camera.hpp camera_sample): 32-bit where the batch allows it (FRT_CAM_FAST; not a
+// strip, whose k_view_rays re-bases pixel_begin per view). B's begin, count, rows and spp are set.
+static void batch_camera_index(const frt_scene_handle* h, frt::Batch& B, int64_t pixels) {
+    const int64_t hs = h->S.cam.hsize;
+    B.cam_fast = h->fk.cam_fast && h->strip_views == 0 &&
+                         frt::cam_index_fits32(B.num_samples, B.pixel_begin, pixels, B.spp, hs, B.row_begin, B.row_stride)
+                     ? 1u
+                     : 0u;
+    if (!B.cam_fast) return;
+    const frt::DivMagic ms = frt::div_magic((uint32_t)B.spp), mh = frt::div_magic((uint32_t)hs);
+    B.spp_magic = ms.magic;
+    B.spp_shift = ms.shift;
+    B.hs_magic = mh.magic;
+    B.hs_shift = mh.shift;
+}
 
 template <typename T>
 static const T* upload(frt_scene_handle* h, const T* src, size_t count, int& rc) {
@@ -3608,7 +3700,7 @@ int frt_scene_upload(const frt_scene* sc, int device, frt_scene_handle** out) {
     S.num_roots = sc->num_roots;
     S.num_lights = sc->num_lights;
     S.num_patterns = sc->num_patterns;
-    S.cam = sc->camera;
+    set_scene_camera(h, sc->camera);
     S.cfg = sc->config;
     h->host_lights.assign(sc->lights, sc->lights + sc->num_lights);
     // the lit list in row order for the first multi-row area / circle light, and its row-ordered shading
@@ -5129,6 +5221,7 @@ static int ensure_light32(frt_scene_handle* h) {
 // store overflow) are not reused by the next frame with the same seed
 static int render_impl(frt_scene_handle* h, const frt_frame_params* P, double* dev_out, frt_frame_stats* st) {
     h->fk = read_frame_knobs();
+    frame_camera_consts(h);
     h->cur_st = st;
     h->rays_walked = 0;
     h->pairs_walked = 0;
@@ -5248,6 +5341,7 @@ static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* 
         B.seed = P->seed;
         B.spp = spp;
         B.stats = st != nullptr ? 1 : 0;
+        batch_camera_index(h, B, bp);
         std::vector<int64_t> count(path + 2, 0);
         count[0] = ns;
         // the queue counts (words 0..15) of every counter line
@@ -5656,6 +5750,7 @@ static int feature_frame(frt_scene_handle* h, const frt_frame_params* P, const f
         B.seed = P->seed;
         B.spp = spp;
         B.stats = st != nullptr ? 1 : 0;
+        batch_camera_index(h, B, bp);
         B.level = 0;
         B.remaining = 0;
         // (the queue k_prepare's signature asks for: nothing is appended to it)
@@ -5720,6 +5815,7 @@ static int feature_frame(frt_scene_handle* h, const frt_frame_params* P, const f
 static int feature_impl(frt_scene_handle* h, const frt_frame_params* P, const frt_feature_buffers* dev,
                         frt_frame_stats* st) {
     h->fk = read_frame_knobs();
+    frame_camera_consts(h);
     h->cur_st = st;
     return feature_frame(h, P, dev, st);
 }
@@ -5789,7 +5885,7 @@ int frt_scene_set_camera(frt_scene_handle* h, const frt_camera* cam, const doubl
         h->S.sample_table = (const double*)p;
         h->host_table.assign(sample_table, sample_table + nt);
     }
-    h->S.cam = *cam;
+    set_scene_camera(h, *cam);
     return 0;
 }
 

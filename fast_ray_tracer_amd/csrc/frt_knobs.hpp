@@ -225,6 +225,11 @@ struct FrameKnobs {
     // FRT_HEAD_KEY0  on  0 off  level 0 stores its keys for a multi-row light (shipped frame 56.4 -> 59.3 ms with the
     //   derived key, profiles/r08_ab_head_cols.txt); off: level 0 derives them there too (A/B, tests/test_head_cols.py)
     bool head_key0 = true;
+    // FRT_CAM_FAST  on  0 off  level 0's camera arithmetic in its cheap exact form: a batch whose sample and pixel
+    //   indices fit 32 bits divides by multiply-shift (frt_cam_index.hpp), and a camera without an aperture takes its
+    //   rays' one origin from the host (DevScene::cam_origin); off: the 64-bit divisions and the origin per ray. The
+    //   same bits either way (tests/test_camera_fast.py; A/B: profiles/r10_ab_camera.txt)
+    bool cam_fast = true;
     // FRT_SHADE_SPLIT  on  "0" off  shading in two kernels (k_shade lists the nodes with light-point work, k_shade_lit
     //   shades them); off: one kernel for every node (A/B)
     bool shade_split = true;
@@ -281,6 +286,7 @@ inline FrameKnobs read_frame_knobs() {
     if (batch > 0) k.batch_samples = (int64_t)batch;
     k.eye_cam = unless_int0("FRT_EYE_CAM");
     k.head_key0 = unless_int0("FRT_HEAD_KEY0");
+    k.cam_fast = unless_int0("FRT_CAM_FAST");
     k.shade_split = unless_str0("FRT_SHADE_SPLIT");
     k.shade_lazy = unless_str0("FRT_SHADE_LAZY");
     k.fuse_resolve = unless_str0("FRT_FUSE_RESOLVE");

@@ -51,6 +51,10 @@ struct Batch {
     int64_t qsegcap;         // entries per segment of this level's queue
     int64_t next_segcap;     // entries per segment of the next level's queue
     const uint32_t* qperm;   // the level's entries in parent order: entry i at storage slot qperm[i]; null: the segments
+    // level 0's index math in 32 bits (frt_camera.hpp camera_sample), decided on the host where the batch is filled
+    // (frt_cam_index.hpp cam_index_fits32, FRT_CAM_FAST): the multiply-shift constants of / spp and / hsize
+    uint32_t cam_fast;       // 0: the 64-bit divisions
+    uint32_t spp_magic, spp_shift, hs_magic, hs_shift;
 };
 
 // storage slot of entry i of the level's queue

@@ -154,6 +154,10 @@ struct DevScene {
     const MeshDesc* meshes;  // WalkNode::op - 1 of a mesh's root group (0: not a mesh)
     int32_t num_meshes;
     int32_t mesh_stack;      // per-lane LDS stack entries of the mesh searches (0: no meshes)
+    // a camera without an aperture: every camera ray's origin, computed once per camera on the host (frt_engine.hip
+    // camera_origin: ray_for_pixel's expression) and used where cam_origin_set (FRT_CAM_FAST, not a strip of views)
+    int32_t cam_origin_set;
+    double cam_origin[3];
 };
 
 enum FeatureBits : int { kFeatCsg = 1, kFeatTorus = 2 };
