@@ -319,6 +319,12 @@ frt_encode_note_device(int device)
     __atomic_store_n(&g_encode_device, device, __ATOMIC_RELAXED);
 }
 
+int
+frt_encode_hint_device(void)
+{
+    return __atomic_load_n(&g_encode_device, __ATOMIC_RELAXED);
+}
+
 static _Thread_local frt_encode_stats t_encode_last;
 
 void

@@ -112,6 +112,46 @@ ENCODE_BACKENDS = ("host", "device", "auto")
 ENCODE_DECLINES = (None, "zero_max", "non_finite", "over_cap", "no_device", "too_large")
 
 
+DENOISE_BACKENDS = ("host", "device", "auto")  # enum frt_denoise_backend, by value
+DENOISE_MAX_ITERATIONS = 8
+
+
+class DenoiseParams(ctypes.Structure):
+    """frt_denoise_params (include/frt_device.h "Denoise"). DenoiseParams() holds the library's defaults
+    (frt_denoise_defaults); keyword arguments replace single fields: DenoiseParams(iterations=3)."""
+    _fields_ = [("iterations", ctypes.c_int32), ("normal_squarings", ctypes.c_int32), ("demodulate", ctypes.c_int32),
+                ("match_material", ctypes.c_int32), ("sigma_color", ctypes.c_double), ("sigma_depth", ctypes.c_double),
+                ("albedo_eps", ctypes.c_double)]
+
+    def __init__(self, **fields):
+        super().__init__()
+        host_lib().frt_denoise_defaults(ctypes.byref(self))
+        for k, v in fields.items():
+            if k not in dict(self._fields_):
+                raise TypeError("frt: DenoiseParams has no field %r" % (k,))
+            setattr(self, k, v)
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class DenoiseStats(ctypes.Structure):
+    """frt_denoise_stats (include/frt_device.h)."""
+    _fields_ = [("pixels", ctypes.c_uint64), ("valid_pixels", ctypes.c_uint64), ("iterations", ctypes.c_int32),
+                ("backend", ctypes.c_int32), ("device", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("upload_ms", ctypes.c_double), ("pack_ms", ctypes.c_double), ("atrous_ms", ctypes.c_double),
+                ("atrous_iter_ms", ctypes.c_double * DENOISE_MAX_ITERATIONS), ("readback_ms", ctypes.c_double),
+                ("host_ms", ctypes.c_double)]
+
+    def as_dict(self) -> dict:
+        return {"pixels": int(self.pixels), "valid_pixels": int(self.valid_pixels),
+                "iterations": int(self.iterations), "backend": DENOISE_BACKENDS[self.backend],
+                "device": int(self.device), "upload_ms": float(self.upload_ms), "pack_ms": float(self.pack_ms),
+                "atrous_ms": float(self.atrous_ms),
+                "atrous_iter_ms": [float(self.atrous_iter_ms[i]) for i in range(self.iterations)],
+                "readback_ms": float(self.readback_ms), "host_ms": float(self.host_ms)}
+
+
 def host_lib(auto_build: bool = False) -> ctypes.CDLL:
     """Load libfrt_host.so (which pulls in libfrt_device.so) with global symbols."""
     global _host
@@ -196,6 +236,23 @@ def host_lib(auto_build: bool = False) -> ctypes.CDLL:
         for fn in ("frt_render_feature_views_device", "frt_render_feature_views_host"):
             getattr(lib, fn).restype = ctypes.c_int
             getattr(lib, fn).argtypes = [vp, vp, ctypes.c_int32, fp, fb, fs]
+        for fn, mirror in (("frt_denoise_params_size", DenoiseParams), ("frt_denoise_stats_size", DenoiseStats)):
+            getattr(lib, fn).restype = ctypes.c_size_t
+            if getattr(lib, fn)() != ctypes.sizeof(mirror):
+                raise RuntimeError("frt: %s() is %d bytes in %s, runtime.py %s %d: rebuild"
+                                   % (fn, getattr(lib, fn)(), build.DEVICE_LIB, mirror.__name__,
+                                      ctypes.sizeof(mirror)))
+        dp, ds, i64 = ctypes.POINTER(DenoiseParams), ctypes.POINTER(DenoiseStats), ctypes.c_int64
+        lib.frt_denoise_defaults.restype = None
+        lib.frt_denoise_defaults.argtypes = [dp]
+        lib.frt_denoise_host.restype = ctypes.c_int
+        lib.frt_denoise_host.argtypes = [vp, vp, vp, i64, i64, i64, dp, vp, ds]
+        lib.frt_denoise_device.restype = ctypes.c_int
+        lib.frt_denoise_device.argtypes = [vp, vp, vp, ctypes.c_int, i64, i64, i64, dp, ctypes.c_int, vp, ds]
+        lib.frt_denoise.restype = ctypes.c_int
+        lib.frt_denoise.argtypes = [vp, vp, vp, ctypes.c_int, i64, i64, i64, dp, ctypes.c_int, ctypes.c_int, vp, ds]
+        lib.frt_denoise_error.restype = ctypes.c_char_p
+        lib.frt_denoise_release.restype = None
         _host = lib
         return lib
 
@@ -503,6 +560,72 @@ class GpuRenderer:
         self.render_into(frame.data_ptr(), **render_args)
         return _encode16(frame.data_ptr(), True, self.frame.width, self.frame.height, mode, "device", self.device)
 
+    def render_denoised(self, params=None, **render_args):
+        """Render the whole frame and its feature buffers into device memory (torch tensors: render_into,
+        render_features_into) and denoise the frame there (frt_denoise on device buffers, in place): nothing crosses
+        to the host in between. Returns ((h, w, 4) float64 array, denoise stats dict): bit for bit
+        denoise(render(...), render_features(...)) with the same arguments. render_args as render_into's (seed,
+        batch_samples, precision; the feature pass takes seed and batch_samples)."""
+        import torch
+        h, w = self.frame.height, self.frame.width
+        with torch.cuda.device(self.device):
+            frame = torch.empty((h, w, 4), dtype=torch.float64, device="cuda")
+            geom = torch.empty((h, w, FEATURE_GEOM_WORDS), dtype=torch.float64, device="cuda")
+            ids = torch.empty((h, w, 2), dtype=torch.int32, device="cuda")
+        self.render_into(frame.data_ptr(), **render_args)
+        self.render_features_into(geom.data_ptr(), ids.data_ptr(),
+                                  **{k: v for k, v in render_args.items() if k in ("seed", "batch_samples")})
+        st = _denoise(frame.data_ptr(), geom.data_ptr(), ids.data_ptr(), True, w, h, 1, params, "device", self.device,
+                      frame.data_ptr())
+        return frame.cpu().numpy(), st.as_dict()
+
+    def render_denoised_views(self, views, params=None, **render_args):
+        """render_denoised of K views of this renderer's world as one strip: render_views' and
+        render_feature_views' passes into device memory, then one denoise call over the K images (a tap never
+        leaves its own view). Returns ((K, h, w, 4) float64 array, denoise stats dict); view k is bit for bit
+        set_camera(views[k]) + render_denoised(...)."""
+        import torch
+        unknown = set(render_args) - {"seed", "batch_samples", "precision"}
+        if unknown:
+            raise TypeError("frt: render_denoised_views takes seed, batch_samples and precision, not %s"
+                            % sorted(unknown))
+        views, cams = self._strip_cams("render_denoised_views", views)
+        lib, first, own = self.lib, views[0], self.frame
+        fb, fp, fs = ctypes.POINTER(FeatureBuffers), ctypes.POINTER(FrameParams), ctypes.POINTER(FrameStats)
+        lib.frt_render_views_device.restype = ctypes.c_int
+        lib.frt_render_views_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, fp, ctypes.c_void_p,
+                                                fs]
+        lib.frt_render_feature_views_device.restype = ctypes.c_int
+        lib.frt_render_feature_views_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, fp, fb, fs]
+        k, h, w = len(views), first.height, first.width
+        with torch.cuda.device(self.device):
+            frame = torch.empty((k, h, w, 4), dtype=torch.float64, device="cuda")
+            geom = torch.empty((k, h, w, FEATURE_GEOM_WORDS), dtype=torch.float64, device="cuda")
+            ids = torch.empty((k, h, w, 2), dtype=torch.int32, device="cuda")
+        # the handle's sample table is the strip's: a strip of other steps borrows the handle for its first view
+        borrow = (first.usteps, first.vsteps) != (own.usteps, own.vsteps)
+        if borrow:
+            self.set_camera(first)
+        try:
+            p = self._params(0, h, 1, render_args.get("seed", 0x5EED), render_args.get("batch_samples", 0),
+                             render_args.get("precision"))
+            rc = lib.frt_render_views_device(self.handle, cams, k, ctypes.byref(p), ctypes.c_void_p(frame.data_ptr()),
+                                             None)
+            if rc == 0:
+                bufs = FeatureBuffers(geom.data_ptr(), ids.data_ptr())
+                p.precision = 0
+                rc = lib.frt_render_feature_views_device(self.handle, cams, k, ctypes.byref(p), ctypes.byref(bufs),
+                                                         None)
+            err = lib.frt_last_error().decode() if rc != 0 else ""
+        finally:
+            if borrow:
+                self.set_camera(own)
+        if rc != 0:
+            raise RuntimeError("frt render_denoised_views failed: " + err)
+        st = _denoise(frame.data_ptr(), geom.data_ptr(), ids.data_ptr(), True, w, h, k, params, "device", self.device,
+                      frame.data_ptr())
+        return frame.cpu().numpy(), st.as_dict()
+
 
 def render_multi(scene: Scene, devices: str | None = None) -> np.ndarray:
     """The drop-in entry point itself: ``render_multi(cam, world, usteps, vsteps, jitter)``
@@ -761,6 +884,77 @@ def encode_selftest(n: int, seed: int = 1):
     out = (ctypes.c_double * 3)()
     bad = host_lib().frt_encode_selftest(n, seed, out, 3)
     return int(bad), list(out)
+
+
+def _denoise_params(params) -> DenoiseParams:
+    if params is None:
+        return DenoiseParams()
+    if isinstance(params, DenoiseParams):
+        return params
+    if isinstance(params, dict):
+        return DenoiseParams(**params)
+    raise TypeError("frt: denoise params must be a DenoiseParams, a dict of its fields or None")
+
+
+def _denoise(rgba: int, geom: int, ids: int, on_device: bool, w: int, h: int, nimages: int, params, backend: str,
+             device: int, out: int) -> DenoiseStats:
+    """frt_denoise on raw pointers (all on the host or all on `device`); raises with the library's reason."""
+    lib = host_lib()
+    if backend not in DENOISE_BACKENDS:
+        raise ValueError("frt: denoise backend %r is not supported (%s)" % (backend, ", ".join(DENOISE_BACKENDS)))
+    p = _denoise_params(params)
+    st = DenoiseStats()
+    rc = lib.frt_denoise(ctypes.c_void_p(rgba), ctypes.c_void_p(geom), ctypes.c_void_p(ids), int(on_device), w, h,
+                         nimages, ctypes.byref(p), DENOISE_BACKENDS.index(backend), device, ctypes.c_void_p(out),
+                         ctypes.byref(st))
+    if rc != 0:
+        raise RuntimeError("frt: denoise failed: " + lib.frt_denoise_error().decode())
+    return st
+
+
+def _feature_buffers(features):
+    """(geom (..., 8) float64, ids (..., 2) int32), C-contiguous, from render_features' dict or a (geom, ids) pair."""
+    if isinstance(features, dict):
+        geom = features["depth"].base if isinstance(features.get("depth"), np.ndarray) else None
+        ids = features["node"].base if isinstance(features.get("node"), np.ndarray) else None
+        shape = features["depth"].shape
+        if geom is None or geom.shape != shape + (FEATURE_GEOM_WORDS,) or geom.dtype != np.float64:
+            geom = np.concatenate([features["depth"][..., None], features["normal"], features["albedo"],
+                                   features["coverage"][..., None]], axis=-1)
+        if ids is None or ids.shape != shape + (2,) or ids.dtype != np.int32:
+            ids = np.stack([features["node"], features["material"]], axis=-1)
+    else:
+        geom, ids = features
+    return (np.ascontiguousarray(geom, dtype=np.float64), np.ascontiguousarray(ids, dtype=np.int32))
+
+
+def denoise(rgba: np.ndarray, features, params=None, backend: str = "device", device: int = 0, stats: bool = False):
+    """Denoise a colour frame with its first-hit feature buffers (frt_denoise: an edge-avoiding a-trous filter
+    guided by depth, normal, albedo and material id; include/frt_device.h "Denoise"). rgba: (h, w, 4) float64, or
+    (K, h, w, 4) for K stacked views, which are filtered independently; features: render_features' /
+    render_feature_views' dict, or a (geom (..., 8) float64, ids (..., 2) int32) pair. params: a DenoiseParams, a
+    dict of its fields, or None for the defaults. backend "device": the HIP pass (frt_denoise.hip); "host": the C
+    pass, which is the definition; "auto": the device once this process has rendered on one. The two give the same
+    bits. A missing device is an error, not a fall-back. Returns a new array like rgba (with stats=True: and the
+    DenoiseStats). Pixels without a hit, or with a non-finite colour, come back as they are."""
+    rgba = np.ascontiguousarray(rgba, dtype=np.float64)
+    if rgba.ndim not in (3, 4) or rgba.shape[-1] != 4:
+        raise ValueError("frt: denoise needs an (h, w, 4) or (K, h, w, 4) canvas, not %r" % (rgba.shape,))
+    geom, ids = _feature_buffers(features)
+    if geom.shape != rgba.shape[:-1] + (FEATURE_GEOM_WORDS,) or ids.shape != rgba.shape[:-1] + (2,):
+        raise ValueError("frt: denoise needs feature buffers of the canvas's shape: geom %r, ids %r, canvas %r"
+                         % (geom.shape, ids.shape, rgba.shape))
+    k = rgba.shape[0] if rgba.ndim == 4 else 1
+    h, w = rgba.shape[-3], rgba.shape[-2]
+    out = np.empty_like(rgba)
+    st = _denoise(rgba.ctypes.data, geom.ctypes.data, ids.ctypes.data, False, w, h, k, params, backend, device,
+                  out.ctypes.data)
+    return (out, st) if stats else out
+
+
+def denoise_release() -> None:
+    """Free the device pass's buffers (frt_denoise_release); the next call allocates them again."""
+    host_lib().frt_denoise_release()
 
 
 class _CanvasStruct(ctypes.Structure):  # struct canvas (host/src/libs/canvas/canvas.h)

@@ -506,6 +506,93 @@ void frt_encode_release(void);
  */
 int64_t frt_encode_selftest(int64_t n, uint64_t seed, double *out, int nout);
 
+/*
+ * Denoise (fast_ray_tracer_amd/csrc/frt_denoise.hip, host/frt_denoise.c; DESIGN.md "Denoise"): an edge-avoiding
+ * a-trous filter (Dammertz et al. 2010) over a colour frame, guided by the first-hit feature buffers. The host pass
+ * (frt_denoise_host, libfrt_host) is the definition; the device pass repeats it operation for operation in binary64
+ * (+ - * / and comparisons only, no fused multiply-add), so the two agree bit for bit.
+ *
+ * Inputs: nimages images of h x w pixels, stacked view-major. rgba 4 doubles per pixel, geom 8 doubles per pixel
+ * (frt_feature_buffers.geom), ids 2 int32 per pixel (frt_feature_buffers.ids).
+ * A pixel is valid when ids.node >= 0, depth is finite and > 0, the three colour channels are finite (and its
+ * material id is not INT32_MIN, which the guide columns reserve). An invalid pixel is never filtered and never a tap:
+ * its output is its input bit for bit. Taps never leave the pixel's own image.
+ * Per valid pixel once: a[ch] = albedo[ch] + albedo_eps (demodulate) or 1.0; x[ch] = rgb[ch] / a[ch];
+ * nn = (n0*n0 + n1*n1) + n2*n2; inv_nn = nn > 0 ? 1/nn : 0; iz = 1/depth.
+ * Iteration i = 0 .. iterations-1 with step s = 2^i: the 5 x 5 taps q = p + s*(dx, dy), dy outside and dx inside,
+ * ascending, B3 spline weights hk = K[|dx|] * K[|dy|] with K = {3/8, 1/4, 1/16}. The centre tap weighs hk; another
+ * valid tap inside the image is skipped when match_material and the materials differ, or when d = n_p . n_q <= 0;
+ * else t = min((d*d) * (inv_nn_p*inv_nn_q), 1.0) squared normal_squarings times, r = z_p - z_q,
+ * xz = ((r*r) * kz) * (iz_p*iz_q), xc = |x_p - x_q|^2 * kc_i, u = (1 + xz) * (1 + xc), weight (hk*t) / (u*u), with
+ * kz = 1/sigma_depth^2 and kc_i = ldexp(1/sigma_color^2, 2*i). x_{i+1} = sum(weight * x_q) / sum(weight).
+ * Output: rgb = x_N * a on valid pixels, alpha copied. out may be rgba itself.
+ */
+enum frt_denoise_backend { FRT_DENOISE_HOST = 0, FRT_DENOISE_DEVICE = 1, FRT_DENOISE_AUTO = 2 };
+
+#define FRT_DENOISE_MAX_ITERATIONS 8
+#define FRT_DENOISE_MAX_SQUARINGS 8
+
+typedef struct frt_denoise_params {
+    int32_t iterations;       /* 1..8 (default 5): a-trous passes, steps 1, 2, 4, .. */
+    int32_t normal_squarings; /* 0..8 (default 5): the normal term is cos^2 raised to 2^normal_squarings */
+    int32_t demodulate;       /* 0 or 1 (default 1): filter rgb / (albedo + albedo_eps) */
+    int32_t match_material;   /* 0 or 1 (default 1): taps of another material id weigh 0 */
+    double sigma_color;       /* > 0 (default 1.0) */
+    double sigma_depth;       /* > 0 (default 0.1): relative depth difference */
+    double albedo_eps;        /* > 0 (default 2^-10) */
+} frt_denoise_params;
+
+typedef struct frt_denoise_stats {
+    uint64_t pixels;        /* w * h * nimages */
+    uint64_t valid_pixels;
+    int32_t iterations;
+    int32_t backend;        /* enum frt_denoise_backend: who produced out */
+    int32_t device;         /* the HIP device used, -1 when none */
+    int32_t reserved;       /* 0 */
+    double upload_ms;       /* the three inputs to the device (0 when they were there) */
+    double pack_ms;         /* k_denoise_pack (HIP events) */
+    double atrous_ms;       /* the a-trous launches together */
+    double atrous_iter_ms[FRT_DENOISE_MAX_ITERATIONS]; /* each launch */
+    double readback_ms;     /* out (and the valid counts) to the host */
+    double host_ms;         /* the host pass, when it produced out */
+} frt_denoise_stats;
+
+size_t frt_denoise_params_size(void);
+size_t frt_denoise_stats_size(void);
+void frt_denoise_defaults(frt_denoise_params *params);
+
+/*
+ * The refusals every denoise entry point shares (no device needed): a null rgba / geom / ids / params / out; w, h or
+ * nimages <= 0; more than 2^31 - 1 pixels in total; a parameter outside its range; a sigma or albedo_eps that is not
+ * finite. Returns 0, or -1 with the reason in frt_denoise_error().
+ */
+int frt_denoise_check(const double *rgba, const double *geom, const int32_t *ids, int64_t w, int64_t h,
+                      int64_t nimages, const frt_denoise_params *params, const double *out);
+
+/*
+ * The device pass. The four buffers are all in host memory (on_device 0: they are uploaded, out read back) or all in
+ * device memory on `device`. stats may be NULL. Returns 0, or -1 (a refusal above, no such device, a HIP error:
+ * frt_denoise_error); a refusal leaves out untouched. The pass keeps 100 bytes of scratch per pixel on the device
+ * between calls (plus 104 for host buffers) until frt_denoise_release().
+ */
+int frt_denoise_device(const double *rgba, const double *geom, const int32_t *ids, int on_device, int64_t w, int64_t h,
+                       int64_t nimages, const frt_denoise_params *params, int device, double *out,
+                       frt_denoise_stats *stats);
+
+/* message of this thread's last failing denoise call */
+const char *frt_denoise_error(void);
+/* (libfrt_host's passes report through the same message) */
+void frt_denoise_set_error(const char *message);
+
+/* copy `bytes` of host memory to device memory on `device` (the host pass's result for device-resident buffers) */
+int frt_denoise_store(void *device_ptr, const void *host, size_t bytes, int device);
+
+/* free the denoise's device buffers (kept between calls, per device) */
+void frt_denoise_release(void);
+
+/* The host pass (frt_denoise_host) and the entry point that picks a backend (frt_denoise) are libfrt_host's:
+ * fast_ray_tracer_amd/host/frt_denoise.h. */
+
 #ifdef __cplusplus
 }
 #endif
