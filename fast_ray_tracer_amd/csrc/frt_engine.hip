@@ -597,6 +597,32 @@ k_prepare(DevScene S, Batch B, const QueuedRay* __restrict__ q, int64_t n, const
     if (tbox != nullptr) tile_box(node, n, hit, op, tbox, tile_log2, stbox, sub_log2);
 }
 
+// the super-tile boxes of a level: one thread per run of 2^nt_log2 consecutive tiles, the union of their boxes (lo by
+// fminf, hi by fmaxf: outward-rounded boxes stay outward-rounded, an empty tile box (lo = +inf, hi = -inf) is neutral,
+// and a run without a live node stays empty); ntiles: the tiles k_prepare wrote, the last run may hold fewer
+__global__ void __launch_bounds__(kBlock)
+k_sup_boxes(const float* __restrict__ tbox, int64_t ntiles, int nt_log2, float* __restrict__ supbox, int64_t nsup) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= nsup) return;
+    float lo[3] = {__builtin_huge_valf(), __builtin_huge_valf(), __builtin_huge_valf()};
+    float hi[3] = {-__builtin_huge_valf(), -__builtin_huge_valf(), -__builtin_huge_valf()};
+    const int64_t t0 = s << nt_log2, t1 = min(t0 + ((int64_t)1 << nt_log2), ntiles);
+    for (int64_t t = t0; t < t1; ++t) {
+        const float* b = tbox + 6 * t;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = fminf(lo[a], b[a]);
+            hi[a] = fmaxf(hi[a], b[a + 3]);
+        }
+    }
+    float* o = supbox + 6 * s;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        o[a] = lo[a];
+        o[a + 3] = hi[a];
+    }
+}
+
 // one lane per (node, light sample j); lanes of a node are consecutive
 #ifdef FRT_SHADOW_WAVES
 #define FRT_SHADOW_ATTR __attribute__((amdgpu_waves_per_eu(FRT_SHADOW_WAVES, 8)))
@@ -2343,7 +2369,15 @@ struct frt_scene_handle {
     uint32_t* s2list = nullptr;        // the sub-tile pairs left mixed (frt_jit_subtile's list)
     int64_t s2list_cap = 0;
     uint64_t subtile_pairs = 0, subtile_mixed = 0;
-    float* tbox = nullptr;             // the level's tile boxes (k_prepare): 6 floats per tile
+    void* jit_split = nullptr;         // split kernel (frt_jit_split): the module's lists carry (super-tile, tile) entries
+    int sup = 0;                       // path nodes per super-tile (frt_jit_supertile) with jit_split, else 0
+    bool sup_on = false;               // the levels decide super-tiles first, until the split kernel's launch fails
+    float* supbox = nullptr;           // the level's super-tile boxes (k_sup_boxes over tbox): 6 floats per super-tile
+    int64_t supbox_cap = 0;
+    uint32_t* xlist = nullptr;         // the (tile, sample) pairs frt_jit_split leaves mixed
+    int64_t xlist_cap = 0;
+    frt_shadow_stage_stats stages{};   // the last frame's per-stage counters (frt_shadow_stages)
+    float* tbox = nullptr;            // the level's tile boxes (k_prepare): 6 floats per tile
     int64_t tbox_cap = 0;
     uint32_t* tlist = nullptr;         // undecided (tile, light part) pairs, kMixSegs segments
     int64_t tlist_cap = 0;
@@ -2353,8 +2387,8 @@ struct frt_scene_handle {
     const float* light_aabb = nullptr; // per light, per cache row: the points' box (binary32, outward)
     uint32_t* mixed = nullptr;         // mixed (node, light) pairs, kMixSegs segments
     int64_t mixed_cap = 0;
-    unsigned* mcount = nullptr;        // the segments' counters (kMixSegs lines of kMixLine words): four regions, one per
-                                       // stage of a shadow pass (tile, sub-part, sub-tile, node pairs), zeroed together
+    unsigned* mcount = nullptr;        // the segments' counters (kMixSegs lines of kMixLine words): five regions, one per
+                                       // stage of a shadow pass (tile, sub-part, sub-tile, node pairs, split), zeroed together
     uint64_t sync_epoch = 0;           // stream_sync calls (the level loop's early counter read-back)
     PinnedBuf<unsigned> host_mcount;
     PinnedBuf<unsigned long long> host_counters;  // (the level's queue counters, read back per level)
@@ -3332,6 +3366,21 @@ int frt_photon_pass_stats(int64_t* out, int n) {
 
 size_t frt_frame_stats_size(void) { return sizeof(frt_frame_stats); }
 
+size_t frt_shadow_stages(const frt_scene_handle* h, frt_shadow_stage_stats* out) {
+    if (h != nullptr && out != nullptr) {
+        *out = h->stages;
+        out->supertile = h->sup_on ? (uint64_t)h->sup : 0;
+        out->tile_pairs = h->tile_pairs;
+        out->tile_mixed = h->tile_mixed;
+        out->sub_pairs = h->sub_pairs;
+        out->sub_mixed = h->sub_mixed;
+        out->subtile_pairs = h->subtile_pairs;
+        out->subtile_mixed = h->subtile_mixed;
+        out->rays_walked = h->rays_walked;
+    }
+    return sizeof(frt_shadow_stage_stats);
+}
+
 // a stream frt_device_warmup created, handed to the device's next frt_scene_upload (a process's first streams cost
 // 10-160 ms each: tools/warmup_probe.py, profiles/r05_warmup_probe.txt)
 static std::mutex g_warm_mu;
@@ -3529,6 +3578,9 @@ int frt_scene_upload(const frt_scene* sc, int device, frt_scene_handle** out) {
             // (the closest-hit kernel writes n1 = n2 = 1: scenes with refractive indices other than one keep k_trace)
             h->jit_trace = sc->config.all_ni_one ? fns.trace : nullptr;
             h->subtile = fns.subtile ? K.jit_subtile : 0;
+            h->jit_split = fns.split;
+            h->sup = fns.split && h->tile > 0 && h->sub > 0 ? frt_jit_supertile(K) : 0;
+            h->sup_on = h->sup > 0;
             if (h->jit_shadow) {
                 h->redo_cap = 1u << 20;
                 void* p = nullptr;
@@ -3623,7 +3675,7 @@ int frt_scene_upload(const frt_scene* sc, int device, frt_scene_handle** out) {
                     h->light_psamp2 = upload(h, ps2.data(), ps2.size(), rc);
                     h->light_sbox = upload(h, sbox.data(), sbox.size(), rc);
                 }
-                if (rc || hipMalloc((void**)&h->mcount, 4 * frt::jit::kMixSegs * frt::jit::kMixLine * sizeof(unsigned)) != hipSuccess) {
+                if (rc || hipMalloc((void**)&h->mcount, 5 * frt::jit::kMixSegs * frt::jit::kMixLine * sizeof(unsigned)) != hipSuccess) {
                     frt_scene_release(h);
                     return fail("frt_scene_upload: light box / pair list allocation failed");
                 }
@@ -3797,6 +3849,14 @@ void frt_scene_release(frt_scene_handle* h) {
             if (spairs)
                 std::fprintf(stderr, "frt jit stats: sub-part pair kernel (%d sub-parts): live sub-pairs %llu, mixed %llu (%.2f%%)\n",
                              h->sub, spairs, smixed, 100.0 * (double)smixed / (double)spairs);
+            unsigned long long xpairs = 0, xmixed = 0;
+            for (int j = 0; j < 64; ++j) {
+                xpairs += c[32 * j + 10];
+                xmixed += c[32 * j + 11];
+            }
+            if (xpairs)
+                std::fprintf(stderr, "frt jit stats: split kernel (%d nodes per super-tile): live tile sub-pairs %llu, mixed %llu (%.2f%%)\n",
+                             h->sup, xpairs, xmixed, 100.0 * (double)xmixed / (double)xpairs);
             if (upairs)
                 std::fprintf(stderr, "frt jit stats: sub-tile pair kernel (%d nodes per sub-tile): live sub-tile pairs %llu, mixed %llu (%.2f%%)\n",
                              h->subtile, upairs, umixed, 100.0 * (double)umixed / (double)upairs);
@@ -3875,6 +3935,8 @@ void frt_scene_release(frt_scene_handle* h) {
     hip_ignore(hipFree(h->s2list));
     hip_ignore(hipFree(h->tredo));
     hip_ignore(hipFree(h->tbox));
+    hip_ignore(hipFree(h->supbox));
+    hip_ignore(hipFree(h->xlist));
     hip_ignore(hipFree(h->err));
     for (hipEvent_t e : h->ev_pool) hip_ignore(hipEventDestroy(e));
     if (h->ev[0]) hip_ignore(hipEventDestroy(h->ev[0]));
@@ -4158,16 +4220,22 @@ static void launch_shadow(frt_scene_handle* h, const frt::Batch& B, const frt::H
             // sub-tile, and node pairs node * NP + part where a level's list goes to the node pair kernel: a level
             // runs in one range while both fit 32 bits — the headline's level 0, 132.7 M nodes, in one range instead
             // of four, a quarter of the stage launches and host round trips)
+            // (with super-tiles the entries are (((super-tile * NP + part) * sub + q) << log2(super-tile / tile), then the
+            // sub-tile bits: as many entries per node as without, counted per super-tile)
+            const int run = h->sup > h->tile ? h->sup : h->tile;
+            const int fine = h->subtile > 0 && h->subtile < h->tile ? h->subtile : h->tile;
             int stl = 0;
-            while (h->subtile > 0 && (1 << stl) < h->tile / h->subtile) ++stl;
+            while ((fine << stl) < run) ++stl;
             const uint64_t per_tile = ((uint64_t)NP * (uint64_t)h->sub) << stl;
-            const int64_t tiled_max = (int64_t)(0xFFFFFFFFull / per_tile) * h->tile * NP;
+            const int64_t tiled_max = (int64_t)(0xFFFFFFFFull / per_tile) * run * NP;
             kMaxPairs = std::min<int64_t>(std::min<int64_t>(tiled_max, (int64_t)0xFFFFFFFFll),
                                           mp ? mp : INT64_MAX);
         }
         if (n * NP > kMaxPairs) {
             int64_t per = std::max<int64_t>(1, kMaxPairs / NP);
-            if (h->tile > 0) per = std::max<int64_t>(h->tile, per / h->tile * h->tile);
+            // (ranges start at tile boundaries, with super-tiles at theirs)
+            const int64_t unit = h->sup > h->tile ? h->sup : h->tile;
+            if (unit > 0) per = std::max<int64_t>(unit, per / unit * unit);
             for (int64_t off = 0; off < n; off += per)
                 launch_shadow(h, B, rec.at(off), std::min(per, n - off), counts + off * h->S.num_lights, node0 + off);
             return;
@@ -4180,7 +4248,8 @@ static void launch_shadow(frt_scene_handle* h, const frt::Batch& B, const frt::H
         unsigned* mc_sub = h->mcount + kMixSegs * kMixLine;
         unsigned* mc_subtile = h->mcount + 2 * kMixSegs * kMixLine;
         unsigned* mc_node = h->mcount + 3 * kMixSegs * kMixLine;
-        if (beam_on) hip_ignore(hipMemsetAsync(h->mcount, 0, 4 * kMixSegs * kMixLine * sizeof(unsigned), h->stream));
+        unsigned* mc_split = h->mcount + 4 * kMixSegs * kMixLine;
+        if (beam_on) hip_ignore(hipMemsetAsync(h->mcount, 0, 5 * kMixSegs * kMixLine * sizeof(unsigned), h->stream));
         uint64_t total_mixed = 0;
         const uint32_t* direct_in = nullptr;  // (the sub / sub-tile list walked by the per-ray kernel directly)
         uint32_t direct_subq = 0, direct_nodes = 0;
@@ -4194,8 +4263,16 @@ static void launch_shadow(frt_scene_handle* h, const frt::Batch& B, const frt::H
             const float* list_boxes = h->light_aabb;
             int tl = 0;
             while ((1 << tl) < h->tile) ++tl;
+            // super-tiles first (FRT_JIT_SUPERTILE; fk.jit_supertile_deep off: at level 0 only): the tile and sub-part
+            // kernels on runs of sup nodes from the super-tile boxes, then frt_jit_split on the (super-tile, sample)
+            // pairs left, one lane per tile of the run; the later stages see (tile, sample) entries either way
+            const bool use_sup = subbed && h->sup > h->tile && h->sup_on && h->jit_split && h->supbox &&
+                                 (B.level == 0 || h->fk.jit_supertile_deep);
+            int rl = tl;  // (log2 of the nodes per run of the first two stages)
+            while (use_sup && (1 << rl) < h->sup) ++rl;
+            uint32_t runl = (uint32_t)rl;
             if (tiled) {
-                const int64_t ntiles = (n + h->tile - 1) >> tl;
+                const int64_t ntiles = (n + ((int64_t)1 << rl) - 1) >> rl;  // (the first stage's runs)
                 uint32_t ntp = (uint32_t)(ntiles * NP);
                 const int64_t tblocks = (ntiles * NP + frt::kTraceBlock - 1) / frt::kTraceBlock;
                 tsegcap = (uint32_t)std::max<int64_t>(frt::kTraceBlock, ((tblocks + kMixSegs - 1) / kMixSegs) * frt::kTraceBlock);
@@ -4205,12 +4282,12 @@ static void launch_shadow(frt_scene_handle* h, const frt::Batch& B, const frt::H
                     launch_shadow(h, B, rec, n, counts, node0);
                     return;
                 }
-                const float* tb = h->tbox + 6 * (node0 >> tl);
+                const float* tb = use_sup ? h->supbox + 6 * (node0 >> rl) : h->tbox + 6 * (node0 >> tl);
                 const uint32_t* no_list = nullptr;
                 uint32_t zero = 0;
                 void* targs[] = {&h->S, (void*)&B, (void*)&rec, &ntp, &nn, (void*)&tb, (void*)&no_list, &tseg, &zero, &zero,
                                  &h->light_aabb, &counts, &h->tlist, &mc_tile, &tsegcap, &h->err, &h->jit_stats,
-                                 &h->light_psamp2};
+                                 &h->light_psamp2, &runl};
                 hipError_t le;
                 {
                     KTimer tt(h, h->cur_st, 12);
@@ -4257,7 +4334,7 @@ static void launch_shadow(frt_scene_handle* h, const frt::Batch& B, const frt::H
                             uint32_t b0u = (uint32_t)b0;
                             void* sargs[] = {&h->S, (void*)&B, (void*)&rec, &zero, &nn, (void*)&tb, &h->tlist, (void*)&sseg, &b0u,
                                              &tsegcap, &h->light_sbox, &counts, &h->slist, &mc_sub, (void*)&ssegcap, &h->err,
-                                             &h->jit_stats, &h->light_psamp2};
+                                             &h->jit_stats, &h->light_psamp2, &runl};
                             se = hipModuleLaunchKernel((hipFunction_t)h->jit_sub, (unsigned)std::min(max_blocks, sblocks - b0), 1, 1,
                                                        frt::kTraceBlock, 1, 1, 0, h->stream, sargs, nullptr);
                         }
@@ -4281,13 +4358,70 @@ static void launch_shadow(frt_scene_handle* h, const frt::Batch& B, const frt::H
                     const bool subtiled = h->jit_subtile && h->subtile > 0 && h->subtile < h->tile && h->stbox &&
                                           (B.level == 0 || h->fk.jit_subtile_deep);
                     const uint64_t nst = subtiled ? (uint64_t)(h->tile / h->subtile) : 0;
-                    list_blocks = seg_table(h->host_mcount, ssegcap, subtiled ? nst : (uint64_t)h->tile, tseg, listed_s);
+                    // (lanes per (tile, sample) entry of the stage after: its sub-tiles, or its nodes)
+                    const uint64_t after = subtiled ? nst : (uint64_t)h->tile;
+                    const uint64_t nt = use_sup ? (uint64_t)(h->sup / h->tile) : 0;
+                    list_blocks = seg_table(h->host_mcount, ssegcap, use_sup ? nt : after, tseg, listed_s);
                     h->sub_pairs += listed * (uint64_t)h->sub;
                     h->sub_mixed += listed_s;
                     listed = listed_s;
                     list_in = h->slist;
                     list_segcap = ssegcap;
                     list_boxes = h->light_sbox;
+                    if (use_sup && listed_s > 0) {
+                        // the split pass: the (super-tile, sample) pairs left, per tile of the run from the tile's own box,
+                        // resumed from the pair's point; what it leaves is the (tile, sample) list of a level without
+                        // super-tiles
+                        const uint64_t xblocks = list_blocks;
+                        const frt::jit::SegTable xseg = tseg;
+                        const uint32_t xsegcap = (uint32_t)std::max<uint64_t>(
+                            frt::kTraceBlock, ((xblocks + kMixSegs - 1) / kMixSegs) * frt::kTraceBlock);
+                        if (grow(&h->xlist, h->xlist_cap, 2 * (int64_t)xsegcap * kMixSegs)) {  // (out of memory)
+                            (void)hipGetLastError();
+                            h->jit_shadow = nullptr;
+                            hip_ignore(hipMemsetAsync(counts, 0, (size_t)n * h->S.num_lights * sizeof(int32_t), h->stream));
+                            launch_shadow(h, B, rec, n, counts, node0);
+                            return;
+                        }
+                        const float* tileb = h->tbox + 6 * (node0 >> tl);
+                        hipError_t xe = hipSuccess;
+                        {
+                            KTimer tx(h, h->cur_st, 19);
+                            const uint64_t max_blocks = ((1ull << 31) - 1) / frt::kTraceBlock;
+                            uint32_t zero = 0;
+                            for (uint64_t b0 = 0; b0 < xblocks && xe == hipSuccess; b0 += max_blocks) {
+                                uint32_t b0u = (uint32_t)b0;
+                                void* xargs[] = {&h->S, (void*)&B, (void*)&rec, &zero, &nn, (void*)&tileb, &h->slist, (void*)&xseg,
+                                                 &b0u, (void*)&ssegcap, &h->light_sbox, &counts, &h->xlist, &mc_split,
+                                                 (void*)&xsegcap, &h->err, &h->jit_stats, &h->light_psamp2, &runl};
+                                xe = hipModuleLaunchKernel((hipFunction_t)h->jit_split, (unsigned)std::min(max_blocks, xblocks - b0),
+                                                           1, 1, frt::kTraceBlock, 1, 1, 0, h->stream, xargs, nullptr);
+                            }
+                        }
+                        if (xe != hipSuccess) {
+                            std::fprintf(stderr, "frt: scene-specialised split kernel launch failed (%s); no super-tiles\n",
+                                         hipGetErrorString(xe));
+                            (void)hipGetLastError();
+                            h->sup_on = false;
+                            hip_ignore(hipMemsetAsync(counts, 0, (size_t)n * h->S.num_lights * sizeof(int32_t), h->stream));
+                            launch_shadow(h, B, rec, n, counts, node0);
+                            return;
+                        }
+                        if (hipMemcpyAsync(h->host_mcount.data(), mc_split, h->host_mcount.size() * sizeof(unsigned),
+                                           hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+                            stream_sync(h) != hipSuccess)
+                            return;
+                        uint64_t listed_x = 0;
+                        list_blocks = seg_table(h->host_mcount, xsegcap, after, tseg, listed_x);
+                        h->stages.split_pairs += listed_s * nt;
+                        h->stages.split_mixed += listed_x;
+                        listed = listed_s = listed_x;
+                        list_in = h->xlist;
+                        list_segcap = xsegcap;
+                    }
+                    // (the (tile, sample) list the sub-tile stage takes: the sub-part stage's, or the split stage's)
+                    const uint32_t* const ts_list = list_in;
+                    const uint32_t ts_segcap = list_segcap;
                     if (subtiled && listed_s > 0) {
                         // the sub-tile pass: the tile sub-pairs left, per sub-tile of the tile, from its own origin box
                         const uint64_t tblocks = list_blocks;
@@ -4311,9 +4445,9 @@ static void launch_shadow(frt_scene_handle* h, const frt::Batch& B, const frt::H
                             uint32_t zero = 0;
                             for (uint64_t b0 = 0; b0 < tblocks && ue == hipSuccess; b0 += max_blocks) {
                                 uint32_t b0u = (uint32_t)b0;
-                                void* uargs[] = {&h->S, (void*)&B, (void*)&rec, &zero, &nn, (void*)&stb, &h->slist, (void*)&s1seg,
-                                                 &b0u, (void*)&ssegcap, &h->light_sbox, &counts, &h->s2list, &mc_subtile,
-                                                 (void*)&s2segcap, &h->err, &h->jit_stats, &h->light_psamp2};
+                                void* uargs[] = {&h->S, (void*)&B, (void*)&rec, &zero, &nn, (void*)&stb, (void*)&ts_list, (void*)&s1seg,
+                                                 &b0u, (void*)&ts_segcap, &h->light_sbox, &counts, &h->s2list, &mc_subtile,
+                                                 (void*)&s2segcap, &h->err, &h->jit_stats, &h->light_psamp2, &runl};
                                 ue = hipModuleLaunchKernel((hipFunction_t)h->jit_subtile, (unsigned)std::min(max_blocks, tblocks - b0),
                                                            1, 1, frt::kTraceBlock, 1, 1, 0, h->stream, uargs, nullptr);
                             }
@@ -4384,7 +4518,7 @@ static void launch_shadow(frt_scene_handle* h, const frt::Batch& B, const frt::H
                         uint32_t b0u = (uint32_t)b0;
                         void* largs[] = {&h->S, (void*)&B, (void*)&rec, &zero, &nn, (void*)&no_box, (void*)&list_in, &tseg, &b0u,
                                          &list_segcap, (void*)&list_boxes, &counts, nout, &mc_node, &segcap, &h->err,
-                                         &h->jit_stats, &h->light_psamp2};
+                                         &h->jit_stats, &h->light_psamp2, &runl};
                         le = hipModuleLaunchKernel((hipFunction_t)h->jit_list, (unsigned)std::min(max_blocks, list_blocks - b0), 1, 1,
                                                    frt::kTraceBlock, 1, 1, 0, h->stream, largs, nullptr);
                     }
@@ -4397,7 +4531,7 @@ static void launch_shadow(frt_scene_handle* h, const frt::Batch& B, const frt::H
                     uint32_t zero = 0;
                     void* bargs[] = {&h->S, (void*)&B, (void*)&rec, &np, &nn, (void*)&no_box, (void*)&no_list, &no_seg, &zero, &zero,
                                      &h->light_aabb, &counts, nout, &mc_node, &segcap, &h->err, &h->jit_stats,
-                                     &h->light_psamp2};
+                                     &h->light_psamp2, &runl};
                     le = hipModuleLaunchKernel((hipFunction_t)h->jit_beam, grid_for(npairs, frt::kTraceBlock), 1, 1,
                                                frt::kTraceBlock, 1, 1, 0, h->stream, bargs, nullptr);
                     h->node_pairs += (uint64_t)npairs;
@@ -5228,6 +5362,7 @@ static int render_impl(frt_scene_handle* h, const frt_frame_params* P, double* d
     h->heads_walked = 0;
     h->tile_pairs = h->tile_mixed = h->node_pairs = h->node_mixed = h->sub_pairs = h->sub_mixed = 0;
     h->subtile_pairs = h->subtile_mixed = 0;
+    h->stages = frt_shadow_stage_stats{};
     const int rc = render_frame(h, P, dev_out, st);
     if (rc) h->gi.built = false;
     return rc;
@@ -5403,6 +5538,16 @@ static int render_frame(frt_scene_handle* h, const frt_frame_params* P, double* 
                                    subtiles ? h->stbox : nullptr, stl, L.counts, dense ? h->spawn_masks : nullptr,
                                    h->up.prepare_uniform ? 1 : 0);
                 FRT_HIP(hipGetLastError());
+                // the super-tile boxes of the levels that decide super-tiles first (launch_shadow): over the tile boxes
+                if (tiles && h->sup > h->tile && h->sup_on && (d == 0 || h->fk.jit_supertile_deep)) {
+                    int sl = 0;
+                    while ((1 << sl) < h->sup) ++sl;
+                    const int64_t ntiles = (n + h->tile - 1) >> tl, nsup = (n + h->sup - 1) >> sl;
+                    if (grow(&h->supbox, h->supbox_cap, 6 * (nsup + 1))) return -1;
+                    hipLaunchKernelGGL(k_sup_boxes, dim3(grid_for(nsup)), dim3(kBlock), 0, h->stream, h->tbox, ntiles,
+                                       sl - tl, h->supbox, nsup);
+                    FRT_HIP(hipGetLastError());
+                }
                 if (dense) {
                     hipcub::CountingInputIterator<int64_t> idx(0);
                     hipcub::TransformInputIterator<uint32_t, MaskPopc, hipcub::CountingInputIterator<int64_t>> popc(
@@ -5701,6 +5846,8 @@ static void frame_stats(frt_scene_handle* h, frt_frame_stats* st, unsigned err) 
     st->shadow_subtile_pairs = h->subtile_pairs;
     st->shadow_subtile_mixed = h->subtile_mixed;
     collect_timings(h, st);
+    h->stages.split_ms = st->sub_ms[11];
+    h->stages.split_launches = st->sub_launches[11];
 }
 
 // The features pass (frt_render_features*, frt_render_feature_views*): level 0 only, over the batches render_frame

@@ -20,6 +20,11 @@ std::vector<int> frt_jit_sub_sizes(int c, int Q);
 int frt_jit_sub_ps(int PS, int Q);
 int frt_jit_light_subparts(const frt_light& L, const double* light_points, const std::vector<int32_t>& order, int PS,
                            int Q, std::vector<int32_t>& order2);
+// the nodes per super-tile these knobs give (jit_supertile where it exceeds the tile size and the tile and sub-part
+// stages are on), else 0: no split kernel, the lists' entries by tile
+inline int frt_jit_supertile(const UploadKnobs& K) {
+    return K.jit_tile > 0 && K.jit_sub > 0 && K.jit_supertile > K.jit_tile ? K.jit_supertile : 0;
+}
 // the parts (frt_jit.hip): spatially compact groups of the light's samples; returns the part count
 int frt_jit_light_parts(const frt_light& L, const double* light_points, int PS, std::vector<int32_t>& order);
 
@@ -36,6 +41,7 @@ struct FrtJitFns {
     void* list = nullptr;    // frt_jit_beam_list: the nodes of the listed tile pairs
     void* sub = nullptr;     // frt_jit_sub: the sub-parts of the tile pairs left mixed
     void* subtile = nullptr; // frt_jit_subtile: the sub-tiles of the tile sub-pairs left mixed
+    void* split = nullptr;   // frt_jit_split: the tiles of the (super-tile, sample) pairs left mixed
     void* trace = nullptr;   // frt_jit_trace: closest hit per ray (null where the scene has none)
 };
 // compile with hiprtc for `device` (cached per device and source); 0 on success

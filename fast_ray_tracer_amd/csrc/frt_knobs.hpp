@@ -118,6 +118,15 @@ struct UploadKnobs {
     //   re-decided sample by sample (from the tile's origin box), so the node pair kernel only runs for the
     //   (tile, sample) pairs still mixed
     int jit_sub = 16;
+    // FRT_JIT_SUPERTILE  512  128, 256, 512 or 1024, else 0 (off)  path nodes per super-tile: where it exceeds
+    //   FRT_JIT_TILE and the sub-part stage is on, frt_jit_tile and frt_jit_sub decide runs of this many consecutive
+    //   nodes (at level 0 adjacent pixels' samples) from the union of their tile boxes, and frt_jit_split re-decides
+    //   the (super-tile, sample) pairs left per tile of the run before the sub-tile stage; ignored otherwise. A literal
+    //   of the generated source (the split kernel's lanes, the later stages' entry decoding). Headline frame with every
+    //   level on super-tiles, off / 128 / 256 / 512 / 1024: 27.00 / 25.13 / 24.16 / 23.97 / 23.91 ms; 1024 loses on
+    //   cornell_direct_800_4x4 (2.79 -> 3.00 ms) and gains nothing on the shipped light (56.0 ms; 512: 54.4, 256: 54.2)
+    //   (round 11, profiles/r11_ab_supertile.txt)
+    int jit_supertile = 512;
     // FRT_JIT_INSIDE  on  0 off  the origin-inside shortcut for composite boxes (A/B)
     bool jit_inside = true;
     // FRT_JIT_U32  1  any int  0 bools everywhere, 1 32-bit decision values in the pair kernels' CSG units, 2 in the
@@ -183,6 +192,8 @@ inline UploadKnobs read_upload_knobs() {
     k.jit_subtile_set = present("FRT_JIT_SUBTILE");
     const int sub = int_or("FRT_JIT_SUB", 16);
     k.jit_sub = sub == 2 || sub == 4 || sub == 8 || sub == 16 || sub == 32 ? sub : 0;
+    const int sup = int_or("FRT_JIT_SUPERTILE", 512);
+    k.jit_supertile = sup == 128 || sup == 256 || sup == 512 || sup == 1024 ? sup : 0;
     k.jit_inside = unless_int0("FRT_JIT_INSIDE");
     k.jit_u32 = int_or("FRT_JIT_U32", 1);
     k.jit_order = int_or("FRT_JIT_ORDER", 1);
@@ -248,6 +259,11 @@ struct FrameKnobs {
     int64_t jit_min_pairs = (int64_t)1 << 18;
     // FRT_JIT_SUBTILE_DEEP  on  0 off  off: levels past the camera's walk the sub-part list ray by ray (A/B)
     bool jit_subtile_deep = true;
+    // FRT_JIT_SUPERTILE_DEEP  off  non-zero on  the levels that decide super-tiles first (FRT_JIT_SUPERTILE): level 0
+    //   only, whose nodes are pixel-major, or (on) every level that takes the beam stages; the deeper levels' nodes are
+    //   in parent order. Headline frame: level 0 only 24.13 ms, every level 23.98 ms (0.15 ms, under three spreads of
+    //   0.13 ms); cornell_direct_800_4x4: 2.69 against 2.81 ms (round 11, profiles/r11_ab_supertile.txt)
+    bool jit_supertile_deep = false;
     // FRT_JIT_TRACE (frame side)  on  0 off  use the scene's frt_jit_trace where it has one
     bool jit_trace = true;
     // FRT_JIT_TRACE_STATS  off  set: on  debug: the undecided share per launch (synchronises)
@@ -294,6 +310,7 @@ inline FrameKnobs read_frame_knobs() {
     k.jit_max_pairs = mp >= 1 && mp < (1ll << 31) ? (int64_t)mp : 0;
     k.jit_min_pairs = (int64_t)ll_or("FRT_JIT_MIN_PAIRS", 1ll << 18);
     k.jit_subtile_deep = unless_int0("FRT_JIT_SUBTILE_DEEP");
+    k.jit_supertile_deep = int_or("FRT_JIT_SUPERTILE_DEEP", 0) != 0;
     k.jit_trace = unless_int0("FRT_JIT_TRACE");
     k.jit_trace_stats = present("FRT_JIT_TRACE_STATS");
     if (const char* d = raw("FRT_JIT_TRACE_DUMP")) k.jit_trace_dump = d;

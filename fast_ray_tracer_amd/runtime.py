@@ -52,7 +52,7 @@ class FrameStats(ctypes.Structure):
     def as_dict(self) -> dict:
         names = ["trace", "shadow", "shade", "combine", "resolve", "trace_primary", "prepare", "gi"]
         subs = ["frt_jit_beam", "frt_jit_shadow", "k_gather_est", "k_gather_hit", "frt_jit_tile", "frt_jit_sub",
-                "frt_jit_subtile", "k_shade_lit", "k_lit_sort", "k_shade_lit32", "k_feature_resolve"]
+                "frt_jit_subtile", "k_shade_lit", "k_lit_sort", "k_shade_lit32", "k_feature_resolve", "frt_jit_split"]
         return {
             "primary_rays": int(self.primary_rays), "secondary_rays": int(self.secondary_rays),
             "shadow_rays": int(self.shadow_rays), "pruned_secondary": int(self.pruned_secondary),
@@ -73,6 +73,16 @@ class FrameStats(ctypes.Structure):
             "shadow_subtile_mixed": int(self.shadow_subtile_mixed), "lit_nodes": int(self.lit_nodes),
             "prepare_uniform_waves": int(self.prepare_uniform_waves),
         }
+
+
+class ShadowStageStats(ctypes.Structure):
+    """frt_shadow_stage_stats (include/frt_device.h): the shadow pass's per-stage counters of a handle's last frame."""
+    _fields_ = [(n, ctypes.c_uint64) for n in
+                ("supertile", "tile_pairs", "tile_mixed", "sub_pairs", "sub_mixed", "split_pairs", "split_mixed",
+                 "subtile_pairs", "subtile_mixed", "rays_walked", "split_launches")] + [("split_ms", ctypes.c_double)]
+
+    def as_dict(self) -> dict:
+        return {n: (float if t is ctypes.c_double else int)(getattr(self, n)) for n, t in self._fields_}
 
 
 class FeatureBuffers(ctypes.Structure):
@@ -197,6 +207,10 @@ def host_lib(auto_build: bool = False) -> ctypes.CDLL:
         lib.frt_render_rows_device.restype = ctypes.c_int
         lib.frt_render_rows_device.argtypes = [vp, ctypes.POINTER(FrameParams), vp, ctypes.POINTER(FrameStats)]
         lib.frt_scene_release.argtypes = [vp]
+        lib.frt_shadow_stages.restype = ctypes.c_size_t
+        lib.frt_shadow_stages.argtypes = [vp, ctypes.POINTER(ShadowStageStats)]
+        if lib.frt_shadow_stages(None, None) != ctypes.sizeof(ShadowStageStats):
+            raise RuntimeError("frt: frt_shadow_stage_stats does not match runtime.py ShadowStageStats: rebuild")
         lib.frt_encode_ppm.restype = ctypes.c_size_t
         lib.frt_encode_ppm.argtypes = [vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, vp, ctypes.c_size_t]
         lib.frt_encode16.restype = ctypes.c_int
@@ -430,6 +444,14 @@ class GpuRenderer:
         if rc != 0:
             raise RuntimeError("frt render_views failed: " + err)
         return (out, st) if stats else out
+
+    def shadow_stages(self) -> dict:
+        """The shadow pass's per-stage counters of this renderer's last frame (frt_shadow_stages): the beams each
+        stage tested and left mixed, the rays walked one by one, the super-tile size in use (0: none), and the
+        split stage's launches and HIP-event time where the frame was rendered with stats=True."""
+        st = ShadowStageStats()
+        self.lib.frt_shadow_stages(self.handle, ctypes.byref(st))
+        return st.as_dict()
 
     def close(self) -> None:
         if getattr(self, "handle", None):

@@ -234,7 +234,8 @@ typedef struct frt_frame_stats {
        (sub-tile pair kernel), 7 k_shade_lit (the shading of the path nodes some light reaches; 0 in a fast32 frame), 8 k_lit_scan +
        k_lit_scatter (the lit list in light-row order, multi-row lights), 9 k_shade_lit32 (k_shade_lit's place in a
        fast32 frame; 0 in a parity frame), 10 k_feature_resolve (the features pass, frt_render_features*; 0 in a colour
-       frame); 11-15 unused */
+       frame), 11 frt_jit_split (the tiles of the (super-tile, sample) pairs left mixed; 0 without super-tiles);
+       12-15 unused */
     double sub_ms[16];
     uint64_t sub_launches[16];
     uint64_t shadow_rays_walked;  /* shadow rays walked one by one; the rest of shadow_rays were resolved
@@ -253,6 +254,25 @@ typedef struct frt_frame_stats {
     uint64_t prepare_uniform_waves; /* k_prepare waves whose lanes all hit one leaf and took the scalar path
                                        (FRT_PREPARE_UNIFORM); counted in statistics frames only */
 } frt_frame_stats;
+
+/* The shadow pass's per-stage counters of the handle's last frame (frt_shadow_stages): the beam stages in their
+ * order. With super-tiles (FRT_JIT_SUPERTILE) the first two stages test runs of `supertile` nodes at the levels that
+ * use them, and frt_jit_split the tiles of the pairs they leave; without, split_* are 0. split_ms and
+ * split_launches are filled by frames rendered with statistics (HIP events), like frt_frame_stats.sub_ms. */
+typedef struct frt_shadow_stage_stats {
+    uint64_t supertile;        /* path nodes per super-tile of the handle's kernels, 0: none (or switched off) */
+    uint64_t tile_pairs;       /* (run, light part) beams tested by frt_jit_tile */
+    uint64_t tile_mixed;
+    uint64_t sub_pairs;        /* (run, light sample) beams tested by frt_jit_sub */
+    uint64_t sub_mixed;
+    uint64_t split_pairs;      /* (tile, light sample) beams tested by frt_jit_split */
+    uint64_t split_mixed;
+    uint64_t subtile_pairs;    /* (sub-tile, light sample) beams tested by frt_jit_subtile */
+    uint64_t subtile_mixed;
+    uint64_t rays_walked;      /* shadow rays walked one by one (frt_frame_stats.shadow_rays_walked) */
+    uint64_t split_launches;
+    double split_ms;
+} frt_shadow_stage_stats;
 
 /* number of HIP devices visible (0 when no GPU) */
 int frt_device_count(void);
@@ -274,6 +294,10 @@ size_t frt_frame_stats_size(void);
 
 /* sizeof(frt_frame_params) as this library was built, for the same check (runtime.py FrameParams) */
 size_t frt_frame_params_size(void);
+
+/* the last frame's per-stage shadow counters of `scene` (zeros before its first frame); returns
+ * sizeof(frt_shadow_stage_stats) */
+size_t frt_shadow_stages(const frt_scene_handle *scene, frt_shadow_stage_stats *out);
 
 /* message of the last failing call on this thread */
 const char *frt_last_error(void);
