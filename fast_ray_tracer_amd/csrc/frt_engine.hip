@@ -6103,6 +6103,71 @@ int frt_render_rows(frt_scene_handle* h, const frt_frame_params* P, double* host
     return 0;
 }
 
+// nframes frames under seed, seed + 1, .. into the accumulator (csrc/frt_accum.hip): each is frt_render_rows_device
+// into the accumulator's scratch frame and one add
+int frt_render_rows_accumulate(frt_scene_handle* h, const frt_frame_params* P, int32_t nframes, frt_accum_dev* acc,
+                               frt_frame_stats* st) {
+    if (!h || !P || !acc) return fail("frt_render_rows_accumulate: null argument");
+    if (nframes < 1)
+        return fail("frt_render_rows_accumulate: the number of frames must be positive (got " + std::to_string(nframes) +
+                    ")");
+    if (frt_accum_dev_device(acc) != h->device)
+        return fail("frt_render_rows_accumulate: the accumulator is on device " +
+                    std::to_string(frt_accum_dev_device(acc)) + ", the scene on " + std::to_string(h->device));
+    const int64_t stride = P->row_stride > 0 ? P->row_stride : 1;
+    int64_t nrows = 0;
+    for (int64_t r = P->row_begin; r < P->row_end; r += stride) nrows++;
+    const int64_t npix = nrows * h->S.cam.hsize;
+    if (npix != frt_accum_dev_npixels(acc))
+        return fail("frt_render_rows_accumulate: the accumulator holds " + std::to_string(frt_accum_dev_npixels(acc)) +
+                    " pixels, the frame has " + std::to_string(nrows) + " x " + std::to_string(h->S.cam.hsize));
+    double* frame = frt_accum_dev_frame(acc);
+    if (!frame) return fail(std::string("frt_render_rows_accumulate: ") + frt_accum_error());
+    if (st) std::memset(st, 0, sizeof(*st));
+    frt_frame_params p = *P;
+    for (int32_t k = 0; k < nframes; ++k) {
+        p.seed = P->seed + (uint64_t)k;
+        frt_frame_stats one;
+        if (render_impl(h, &p, frame, st ? &one : nullptr)) return -1;
+        if (frt_accum_dev_add_frame(acc)) return fail(std::string("frt_render_rows_accumulate: ") + frt_accum_error());
+        if (!st) continue;
+        st->primary_rays += one.primary_rays;
+        st->secondary_rays += one.secondary_rays;
+        st->shadow_rays += one.shadow_rays;
+        st->pruned_secondary += one.pruned_secondary;
+        st->hits += one.hits;
+        st->errors += one.errors;
+        st->render_ms += one.render_ms;
+        for (int i = 0; i < 8; ++i) {
+            st->kernel_ms[i] += one.kernel_ms[i];
+            st->kernel_launches[i] += one.kernel_launches[i];
+        }
+        st->shadow_kernel_bytes += one.shadow_kernel_bytes;
+        st->gather_rays += one.gather_rays;
+        st->photons[0] = one.photons[0];
+        st->photons[1] = one.photons[1];
+        st->photon_ms += one.photon_ms;
+        st->shadow_jit = one.shadow_jit;
+        st->photon_pass += one.photon_pass;
+        for (int i = 0; i < 16; ++i) {
+            st->sub_ms[i] += one.sub_ms[i];
+            st->sub_launches[i] += one.sub_launches[i];
+        }
+        st->shadow_rays_walked += one.shadow_rays_walked;
+        st->shadow_tile_pairs += one.shadow_tile_pairs;
+        st->shadow_tile_mixed += one.shadow_tile_mixed;
+        st->shadow_pairs += one.shadow_pairs;
+        st->shadow_pairs_mixed += one.shadow_pairs_mixed;
+        st->shadow_sub_pairs += one.shadow_sub_pairs;
+        st->shadow_sub_mixed += one.shadow_sub_mixed;
+        st->shadow_subtile_pairs += one.shadow_subtile_pairs;
+        st->shadow_subtile_mixed += one.shadow_subtile_mixed;
+        st->lit_nodes += one.lit_nodes;
+        st->prepare_uniform_waves += one.prepare_uniform_waves;
+    }
+    return 0;
+}
+
 size_t frt_feature_geom_words(void) { return 8; }
 
 // the features pass into the handle's own device buffers, then to the host's (either of which may be NULL)

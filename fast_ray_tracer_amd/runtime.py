@@ -162,6 +162,38 @@ class DenoiseStats(ctypes.Structure):
                 "readback_ms": float(self.readback_ms), "host_ms": float(self.host_ms)}
 
 
+class DenoiseVarParams(ctypes.Structure):
+    """frt_denoise_var_params (include/frt_device.h "Variance-guided denoise"). DenoiseVarParams() holds the
+    library's defaults (frt_denoise_var_defaults); keyword arguments replace single fields."""
+    _fields_ = DenoiseParams._fields_ + [("var_eps", ctypes.c_double)]
+
+    def __init__(self, **fields):
+        super().__init__()
+        host_lib().frt_denoise_var_defaults(ctypes.byref(self))
+        for k, v in fields.items():
+            if k not in dict(self._fields_):
+                raise TypeError("frt: DenoiseVarParams has no field %r" % (k,))
+            setattr(self, k, v)
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class DenoiseVarStats(DenoiseStats):
+    """frt_denoise_var_stats (include/frt_device.h): frt_denoise_stats' fields, timed on the var kernels."""
+
+
+class AccumStats(ctypes.Structure):
+    """frt_accum_stats (include/frt_device.h "Accumulator")."""
+    _fields_ = [("pixels", ctypes.c_uint64), ("frames", ctypes.c_uint64), ("skipped", ctypes.c_uint64),
+                ("device", ctypes.c_int32), ("reserved", ctypes.c_int32), ("add_ms", ctypes.c_double),
+                ("resolve_ms", ctypes.c_double)]
+
+    def as_dict(self) -> dict:
+        return {"pixels": int(self.pixels), "frames": int(self.frames), "skipped": int(self.skipped),
+                "device": int(self.device), "add_ms": float(self.add_ms), "resolve_ms": float(self.resolve_ms)}
+
+
 def host_lib(auto_build: bool = False) -> ctypes.CDLL:
     """Load libfrt_host.so (which pulls in libfrt_device.so) with global symbols."""
     global _host
@@ -267,6 +299,39 @@ def host_lib(auto_build: bool = False) -> ctypes.CDLL:
         lib.frt_denoise.argtypes = [vp, vp, vp, ctypes.c_int, i64, i64, i64, dp, ctypes.c_int, ctypes.c_int, vp, ds]
         lib.frt_denoise_error.restype = ctypes.c_char_p
         lib.frt_denoise_release.restype = None
+        for fn, mirror in (("frt_denoise_var_params_size", DenoiseVarParams), ("frt_accum_stats_size", AccumStats)):
+            getattr(lib, fn).restype = ctypes.c_size_t
+            if getattr(lib, fn)() != ctypes.sizeof(mirror):
+                raise RuntimeError("frt: %s() is %d bytes in %s, runtime.py %s %d: rebuild"
+                                   % (fn, getattr(lib, fn)(), build.DEVICE_LIB, mirror.__name__,
+                                      ctypes.sizeof(mirror)))
+        vdp, vds = ctypes.POINTER(DenoiseVarParams), ctypes.POINTER(DenoiseVarStats)
+        lib.frt_denoise_var_defaults.restype = None
+        lib.frt_denoise_var_defaults.argtypes = [vdp]
+        lib.frt_denoise_var_host.restype = ctypes.c_int
+        lib.frt_denoise_var_host.argtypes = [vp, vp, vp, vp, i64, i64, i64, vdp, vp, vp, vds]
+        lib.frt_denoise_var_device.restype = ctypes.c_int
+        lib.frt_denoise_var_device.argtypes = [vp, vp, vp, vp, ctypes.c_int, i64, i64, i64, vdp, ctypes.c_int, vp, vp,
+                                               vds]
+        lib.frt_denoise_var.restype = ctypes.c_int
+        lib.frt_denoise_var.argtypes = [vp, vp, vp, vp, ctypes.c_int, i64, i64, i64, vdp, ctypes.c_int, ctypes.c_int,
+                                        vp, vp, vds]
+        lib.frt_denoise_var_release.restype = None
+        lib.frt_accum_create.restype = ctypes.c_int
+        lib.frt_accum_create.argtypes = [ctypes.c_int, i64, ctypes.POINTER(vp)]
+        lib.frt_accum_reset.restype = ctypes.c_int
+        lib.frt_accum_reset.argtypes = [vp]
+        lib.frt_accum_add.restype = ctypes.c_int
+        lib.frt_accum_add.argtypes = [vp, vp, ctypes.c_int]
+        lib.frt_accum_resolve.restype = ctypes.c_int
+        lib.frt_accum_resolve.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.POINTER(AccumStats)]
+        lib.frt_accum_release.restype = None
+        lib.frt_accum_release.argtypes = [vp]
+        lib.frt_accum_device_part.restype = vp
+        lib.frt_accum_device_part.argtypes = [vp]
+        lib.frt_accum_error.restype = ctypes.c_char_p
+        lib.frt_render_rows_accumulate.restype = ctypes.c_int
+        lib.frt_render_rows_accumulate.argtypes = [vp, fp, ctypes.c_int32, vp, fs]
         _host = lib
         return lib
 
@@ -648,6 +713,67 @@ class GpuRenderer:
                       frame.data_ptr())
         return frame.cpu().numpy(), st.as_dict()
 
+    def _accumulate(self, acc: "Accumulator", frames: int, seed, batch_samples, precision, stats: bool):
+        if frames < 1:
+            raise ValueError("frt: render_accumulated needs frames >= 1, not %r" % (frames,))
+        p = self._params(0, None, 1, seed, batch_samples, precision)
+        st = FrameStats()
+        rc = self.lib.frt_render_rows_accumulate(self.handle, ctypes.byref(p), frames,
+                                                 self.lib.frt_accum_device_part(acc._acc),
+                                                 ctypes.byref(st) if stats else None)
+        if rc != 0:
+            raise RuntimeError("frt render_accumulated failed: " + self.lib.frt_last_error().decode())
+        return st
+
+    def render_accumulated(self, frames: int, seed: int = 0x5EED, batch_samples: int = 0,
+                           precision: str | None = None, stats: bool = False):
+        """Render the whole frame `frames` times under the seeds seed, seed + 1, .. (wrapping uint64) into a device
+        accumulator (frt_render_rows_accumulate: the frames never leave the device) and resolve it. Returns (mean
+        (h, w, 4), var (h, w, 4)) float64: bit for bit what a host Accumulator fed render(seed=seed + k) for
+        k < frames resolves to. var[..., :3] is the variance of the mean (0 where fewer than two frames counted),
+        var[..., 3] the number of frames counted. With stats=True: and the summed FrameStats."""
+        h, w = self.frame.height, self.frame.width
+        acc = Accumulator((h, w), device=self.device)
+        try:
+            st = self._accumulate(acc, frames, seed, batch_samples, precision, stats)
+            mean, var = acc.resolve()
+        finally:
+            acc.close()
+        return (mean, var, st) if stats else (mean, var)
+
+    def render_accumulated_denoised(self, frames: int, params=None, **render_args):
+        """render_accumulated, render_features_into and the variance-guided denoise (frt_denoise_var) on device
+        buffers, in place: nothing crosses to the host in between. Returns (rgba (h, w, 4), var (h, w, 4), denoise
+        stats dict): bit for bit denoise_var(*render_accumulated(frames, ...), render_features(...)). It needs
+        frames >= 2: one frame has no variance, and it raises rather than pass the frame through. render_args: seed,
+        batch_samples, precision (the feature pass takes seed and batch_samples)."""
+        import torch
+        unknown = set(render_args) - {"seed", "batch_samples", "precision"}
+        if unknown:
+            raise TypeError("frt: render_accumulated_denoised takes seed, batch_samples and precision, not %s"
+                            % sorted(unknown))
+        if frames < 2:
+            raise ValueError("frt: render_accumulated_denoised needs frames >= 2 (one frame has no variance), not %r"
+                             % (frames,))
+        h, w = self.frame.height, self.frame.width
+        with torch.cuda.device(self.device):
+            mean = torch.empty((h, w, 4), dtype=torch.float64, device="cuda")
+            var = torch.empty((h, w, 4), dtype=torch.float64, device="cuda")
+            geom = torch.empty((h, w, FEATURE_GEOM_WORDS), dtype=torch.float64, device="cuda")
+            ids = torch.empty((h, w, 2), dtype=torch.int32, device="cuda")
+        acc = Accumulator((h, w), device=self.device)
+        try:
+            self._accumulate(acc, frames, render_args.get("seed", 0x5EED), render_args.get("batch_samples", 0),
+                             render_args.get("precision"), False)
+            acc.resolve_into(mean.data_ptr(), var.data_ptr())
+        finally:
+            acc.close()
+        self.render_features_into(geom.data_ptr(), ids.data_ptr(),
+                                  **{k: v for k, v in render_args.items() if k in ("seed", "batch_samples")})
+        st = _denoise_var(mean.data_ptr(), var.data_ptr(), geom.data_ptr(), ids.data_ptr(), True, w, h, 1, params,
+                          "device", self.device, mean.data_ptr(), var.data_ptr())
+        return mean.cpu().numpy(), var.cpu().numpy(), st.as_dict()
+
 
 def render_multi(scene: Scene, devices: str | None = None) -> np.ndarray:
     """The drop-in entry point itself: ``render_multi(cam, world, usteps, vsteps, jitter)``
@@ -977,6 +1103,127 @@ def denoise(rgba: np.ndarray, features, params=None, backend: str = "device", de
 def denoise_release() -> None:
     """Free the device pass's buffers (frt_denoise_release); the next call allocates them again."""
     host_lib().frt_denoise_release()
+
+
+def _denoise_var_params(params) -> DenoiseVarParams:
+    if params is None:
+        return DenoiseVarParams()
+    if isinstance(params, DenoiseVarParams):
+        return params
+    if isinstance(params, dict):
+        return DenoiseVarParams(**params)
+    raise TypeError("frt: denoise_var params must be a DenoiseVarParams, a dict of its fields or None")
+
+
+def _denoise_var(rgba: int, var: int, geom: int, ids: int, on_device: bool, w: int, h: int, nimages: int, params,
+                 backend: str, device: int, out: int, out_var: int | None) -> DenoiseVarStats:
+    """frt_denoise_var on raw pointers (all on the host or all on `device`); raises with the library's reason."""
+    lib = host_lib()
+    if backend not in DENOISE_BACKENDS:
+        raise ValueError("frt: denoise backend %r is not supported (%s)" % (backend, ", ".join(DENOISE_BACKENDS)))
+    p = _denoise_var_params(params)
+    st = DenoiseVarStats()
+    rc = lib.frt_denoise_var(ctypes.c_void_p(rgba), ctypes.c_void_p(var), ctypes.c_void_p(geom), ctypes.c_void_p(ids),
+                             int(on_device), w, h, nimages, ctypes.byref(p), DENOISE_BACKENDS.index(backend), device,
+                             ctypes.c_void_p(out), ctypes.c_void_p(out_var) if out_var else None, ctypes.byref(st))
+    if rc != 0:
+        raise RuntimeError("frt: denoise_var failed: " + lib.frt_denoise_error().decode())
+    return st
+
+
+def denoise_var(rgba: np.ndarray, var: np.ndarray, features, params=None, backend: str = "device", device: int = 0,
+                stats: bool = False):
+    """Denoise an accumulated mean guided by the variance of that mean (frt_denoise_var: the a-trous filter of
+    denoise() with its colour term scaled by the locally pre-filtered variance, and the variance filtered alongside;
+    include/frt_device.h "Variance-guided denoise"). rgba, var: (h, w, 4) float64 as Accumulator.resolve() /
+    GpuRenderer.render_accumulated return them, or (K, h, w, 4) stacks; features, backend, device as denoise's;
+    params: a DenoiseVarParams, a dict of its fields, or None. Returns (rgba, var) as new arrays (with stats=True:
+    and the DenoiseVarStats). A pixel whose variance and whose neighbours' variance are 0 comes back as it is, as do
+    pixels without a hit or with a non-finite colour or variance."""
+    rgba = np.ascontiguousarray(rgba, dtype=np.float64)
+    var = np.ascontiguousarray(var, dtype=np.float64)
+    if rgba.ndim not in (3, 4) or rgba.shape[-1] != 4:
+        raise ValueError("frt: denoise_var needs an (h, w, 4) or (K, h, w, 4) canvas, not %r" % (rgba.shape,))
+    if var.shape != rgba.shape:
+        raise ValueError("frt: denoise_var needs a variance of the canvas's shape %r, not %r" % (rgba.shape, var.shape))
+    geom, ids = _feature_buffers(features)
+    if geom.shape != rgba.shape[:-1] + (FEATURE_GEOM_WORDS,) or ids.shape != rgba.shape[:-1] + (2,):
+        raise ValueError("frt: denoise_var needs feature buffers of the canvas's shape: geom %r, ids %r, canvas %r"
+                         % (geom.shape, ids.shape, rgba.shape))
+    k = rgba.shape[0] if rgba.ndim == 4 else 1
+    h, w = rgba.shape[-3], rgba.shape[-2]
+    out, out_var = np.empty_like(rgba), np.empty_like(var)
+    st = _denoise_var(rgba.ctypes.data, var.ctypes.data, geom.ctypes.data, ids.ctypes.data, False, w, h, k, params,
+                      backend, device, out.ctypes.data, out_var.ctypes.data)
+    return (out, out_var, st) if stats else (out, out_var)
+
+
+def denoise_var_release() -> None:
+    """Free the variance-guided device pass's buffers (frt_denoise_var_release)."""
+    host_lib().frt_denoise_var_release()
+
+
+class Accumulator:
+    """A per-pixel running mean and variance over frames (frt_accum: Welford's update; include/frt_device.h
+    "Accumulator"). npixels_or_shape: a pixel count, or (h, w), which resolve() then shapes its arrays by. device: a
+    HIP device (the state lives there; add() takes numpy arrays or device pointers) or None for the host pass, which
+    is the definition (numpy arrays only). The two resolve to the same bits."""
+
+    def __init__(self, npixels_or_shape, device: int | None = 0):
+        self.lib = host_lib()
+        self.shape = (int(npixels_or_shape),) if np.isscalar(npixels_or_shape) else tuple(
+            int(n) for n in npixels_or_shape)
+        self.npixels = int(np.prod(self.shape, dtype=np.int64)) if self.shape else 0
+        self.device = device
+        acc = ctypes.c_void_p()
+        if self.lib.frt_accum_create(-1 if device is None else device, self.npixels, ctypes.byref(acc)) != 0:
+            raise RuntimeError("frt: accumulator: " + self.lib.frt_accum_error().decode())
+        self._acc = acc
+
+    def _check(self, rc: int) -> None:
+        if rc != 0:
+            raise RuntimeError("frt: accumulator: " + self.lib.frt_accum_error().decode())
+
+    def add(self, sample) -> None:
+        """One sample per pixel: a float64 array of npixels x 4 values (any shape), or an int, the address of as
+        many doubles in device memory on the accumulator's device (a torch.cuda tensor's data_ptr())."""
+        if isinstance(sample, int):
+            self._check(self.lib.frt_accum_add(self._acc, ctypes.c_void_p(sample), 1))
+            return
+        a = np.ascontiguousarray(sample, dtype=np.float64)
+        if a.size != self.npixels * 4:
+            raise ValueError("frt: accumulator of %d pixels given %d values (4 per pixel)" % (self.npixels, a.size))
+        self._check(self.lib.frt_accum_add(self._acc, a.ctypes.data, 0))
+
+    def resolve(self, stats: bool = False):
+        """(mean, var), float64 arrays of shape + (4,): var[..., :3] the variance of the mean (0.0 under two samples),
+        var[..., 3] the samples counted. With stats=True: and the AccumStats."""
+        mean = np.empty(self.shape + (4,), dtype=np.float64)
+        var = np.empty(self.shape + (4,), dtype=np.float64)
+        st = AccumStats()
+        self._check(self.lib.frt_accum_resolve(self._acc, mean.ctypes.data, var.ctypes.data, 0, ctypes.byref(st)))
+        return (mean, var, st) if stats else (mean, var)
+
+    def resolve_into(self, mean_ptr: int | None, var_ptr: int | None) -> AccumStats:
+        """resolve into device memory on the accumulator's device (npixels x 4 doubles each; either may be None)."""
+        st = AccumStats()
+        self._check(self.lib.frt_accum_resolve(self._acc, ctypes.c_void_p(mean_ptr) if mean_ptr else None,
+                                               ctypes.c_void_p(var_ptr) if var_ptr else None, 1, ctypes.byref(st)))
+        return st
+
+    def reset(self) -> None:
+        self._check(self.lib.frt_accum_reset(self._acc))
+
+    def close(self) -> None:
+        if getattr(self, "_acc", None):
+            self.lib.frt_accum_release(self._acc)
+            self._acc = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class _CanvasStruct(ctypes.Structure):  # struct canvas (host/src/libs/canvas/canvas.h)

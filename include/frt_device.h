@@ -617,6 +617,134 @@ void frt_denoise_release(void);
 /* The host pass (frt_denoise_host) and the entry point that picks a backend (frt_denoise) are libfrt_host's:
  * fast_ray_tracer_amd/host/frt_denoise.h. */
 
+/*
+ * Accumulator (fast_ray_tracer_amd/csrc/frt_accum.hip, host/frt_accum.c; DESIGN.md "Accumulation and the
+ * variance-guided denoise"): the per-pixel running mean and variance of a sequence of frames, Welford's update in
+ * binary64 (+ - * / and comparisons only, no fused multiply-add). The host pass (libfrt_host, host/frt_accum.h) is the
+ * definition; the device pass repeats it operation for operation, so the two agree bit for bit.
+ *
+ * State per pixel: n (int32), mean[4] (r, g, b, a), m2[3]; all zero after create and reset.
+ * Add one sample x (4 doubles): when any of the four is not finite the pixel skips the sample (counted in
+ * frt_accum_stats.skipped). Otherwise n += 1 and for each of the four channels d = x - mean,
+ * mean = mean + d / (double)n; for r, g, b also m2 = m2 + d * (x - mean), with the updated mean.
+ * Resolve: mean_rgba = mean (zeros where n == 0). var, 4 doubles per pixel: channels 0..2
+ * (m2 / (double)(n - 1)) / (double)n, the variance of the mean, 0.0 where n < 2; channel 3 (double)n.
+ *
+ * The device accumulator keeps its state as columns (7 columns of 8 bytes and one of 4: 60 bytes per pixel), a frame
+ * of scratch (32 bytes per pixel; frt_render_rows_accumulate renders into it, host samples are uploaded into it) and,
+ * once a resolve into host memory has run, 64 more for its two outputs. Everything is freed by the release.
+ */
+typedef struct frt_accum_dev frt_accum_dev;
+
+typedef struct frt_accum_stats {
+    uint64_t pixels;
+    uint64_t frames;     /* adds since the create or the last reset */
+    uint64_t skipped;    /* samples skipped since then, over all pixels (a non-finite channel) */
+    int32_t device;      /* the HIP device, -1 for a host accumulator */
+    int32_t reserved;    /* 0 */
+    double add_ms;       /* the last k_accum_add (HIP events; 0 on the host) */
+    double resolve_ms;   /* k_accum_resolve (HIP events), or the host's resolve */
+} frt_accum_stats;
+
+size_t frt_accum_stats_size(void);
+
+/*
+ * Refusals (all return -1 with the reason in frt_accum_error, and leave every output untouched): a null pointer;
+ * npixels <= 0 or more than 2^31 - 1 (the columns' index is 32-bit); no such device. A skipped-sample counter is an
+ * int32 per wave of 64 pixels: an accumulator takes at most 2^25 - 1 adds between resets (more is refused),
+ * so that a wave whose 64 lanes skip every sample stays under 2^31.
+ * rgba, mean_rgba and var are all in host memory (on_device 0: uploaded / read back) or all in device memory on the
+ * accumulator's device. mean_rgba or var may be NULL (not both). stats may be NULL.
+ */
+int frt_accum_dev_create(int device, int64_t npixels, frt_accum_dev **out);
+int frt_accum_dev_reset(frt_accum_dev *acc);
+int frt_accum_dev_add(frt_accum_dev *acc, const double *rgba, int on_device);
+int frt_accum_dev_resolve(frt_accum_dev *acc, double *mean_rgba, double *var, int on_device, frt_accum_stats *stats);
+void frt_accum_dev_release(frt_accum_dev *acc);
+int64_t frt_accum_dev_npixels(const frt_accum_dev *acc);
+int frt_accum_dev_device(const frt_accum_dev *acc);
+/* the accumulator's scratch frame (npixels x 4 doubles of device memory), allocated on first use; NULL on failure */
+double *frt_accum_dev_frame(frt_accum_dev *acc);
+/* frt_accum_dev_add of the scratch frame's contents */
+int frt_accum_dev_add_frame(frt_accum_dev *acc);
+
+/* message of this thread's last failing accumulator call (libfrt_host's passes report through the same message) */
+const char *frt_accum_error(void);
+void frt_accum_set_error(const char *message);
+
+/*
+ * Render nframes frames of the handle's scene into the accumulator, on the device: frame k (0-based) is exactly what
+ * frt_render_rows_device renders with params->seed + k (wrapping uint64) and params otherwise unchanged, into the
+ * accumulator's scratch frame, followed by one add. nframes >= 1; the accumulator is on the handle's device and its
+ * npixels equals rows x width of params. stats (may be NULL) receives the frames' frt_frame_stats with every uint64
+ * counter, every *_ms time, kernel_launches, sub_launches, shadow_kernel_bytes and photon_pass (the frames that
+ * traced their photon maps) summed; photons and shadow_jit are the last frame's. Returns 0, or -1 with the reason in
+ * frt_last_error; frames added before a failure stay added.
+ */
+int frt_render_rows_accumulate(frt_scene_handle *h, const frt_frame_params *params, int32_t nframes,
+                               frt_accum_dev *acc, frt_frame_stats *stats);
+
+/*
+ * Variance-guided denoise (fast_ray_tracer_amd/csrc/frt_denoise_var.hip, host/frt_denoise_var.c; DESIGN.md
+ * "Accumulation and the variance-guided denoise"): the spatial filter of SVGF (Schied et al. 2017) without
+ * reprojection, on an accumulated mean and the variance of that mean. The host pass (frt_denoise_var_host,
+ * libfrt_host) is the definition and the device pass repeats it bit for bit, as for the denoise above, whose
+ * definition holds for everything not mentioned here.
+ *
+ * Inputs: the denoise's three (rgba, geom, ids, stacked over nimages) and var, 4 doubles per pixel as the
+ * accumulator resolves it. Outputs: out (may be rgba itself) and out_var (may be var itself, may be NULL).
+ * Valid: as above, and additionally var[0..2] finite and >= 0.
+ * Pack: as above, plus v[ch] = var[ch] / (a[ch] * a[ch]).
+ * Iteration i, step s = 2^i, on this iteration's colour x and variance v:
+ *   Guide: vs_q = (v0_q + v1_q) + v2_q; g_p = (sum G * vs_q) / (sum G) over the 3 x 3 taps q = p + (dx, dy) at
+ *   distance 1 whatever s is, dy outside and dx inside, ascending, G = {1/2, 1/4}[|dx|] * {1/2, 1/4}[|dy|]; taps outside
+ *   the pixel's own image or invalid are skipped; there is no edge-stopping in this pre-filter.
+ *   kc_p = kc / (g_p + var_eps) with kc = 1 / sigma_color^2, the same at every iteration (no ldexp tightening: the
+ *   shrinking variance does that).
+ *   Taps: the 5 x 5 loop above with xc = ((dc0*dc0 + dc1*dc1) + dc2*dc2) * kc_p; next to acc[ch] += w * x_q[ch] and
+ *   ws += w it accumulates vacc[ch] += (w * w) * v_q[ch]; the centre weighs hk.
+ *   x_{i+1} = acc / ws; v_{i+1}[ch] = vacc[ch] / (ws * ws).
+ * Output: on valid pixels rgb = x_N * a and out_var[ch] = v_N[ch] * (a[ch] * a[ch]); alpha and var[3] are copied.
+ * Invalid pixels are copied bit for bit in both outputs.
+ * A pixel with variance 0 whose neighbours' variance is 0 has kc_p = kc / var_eps: any tap whose colour differs
+ * weighs next to nothing, and the pixel is left alone.
+ */
+typedef struct frt_denoise_var_params {
+    int32_t iterations;       /* 1..8 (default 5) */
+    int32_t normal_squarings; /* 0..8 (default 5) */
+    int32_t demodulate;       /* 0 or 1 (default 1) */
+    int32_t match_material;   /* 0 or 1 (default 1) */
+    double sigma_color;       /* > 0 (default 2.0): in standard deviations of the pre-filtered variance */
+    double sigma_depth;       /* > 0 (default 0.1) */
+    double albedo_eps;        /* > 0 (default 2^-10) */
+    double var_eps;           /* > 0 (default 2^-40) */
+} frt_denoise_var_params;
+
+typedef frt_denoise_stats frt_denoise_var_stats; /* the same fields; pack_ms / atrous_* are the var kernels' */
+
+size_t frt_denoise_var_params_size(void);
+void frt_denoise_var_defaults(frt_denoise_var_params *params);
+
+/* the denoise's refusals (frt_denoise_check) with var among the pointers and var_eps among the parameters; out_var
+ * may be NULL. Returns 0, or -1 with the reason in frt_denoise_error(). */
+int frt_denoise_var_check(const double *rgba, const double *var, const double *geom, const int32_t *ids, int64_t w,
+                          int64_t h, int64_t nimages, const frt_denoise_var_params *params, const double *out);
+
+/*
+ * The device pass; buffers all in host memory (on_device 0) or all in device memory on `device`, as for
+ * frt_denoise_device. It keeps 164 bytes of scratch per pixel on the device between calls (20 columns of 8 bytes, the
+ * material column of 4), plus 136 for host buffers, grow-only, until frt_denoise_var_release().
+ */
+int frt_denoise_var_device(const double *rgba, const double *var, const double *geom, const int32_t *ids,
+                           int on_device, int64_t w, int64_t h, int64_t nimages,
+                           const frt_denoise_var_params *params, int device, double *out, double *out_var,
+                           frt_denoise_var_stats *stats);
+
+/* free the variance-guided denoise's device buffers (kept between calls, per device) */
+void frt_denoise_var_release(void);
+
+/* frt_denoise_var_host and frt_denoise_var (backend choice) are libfrt_host's: host/frt_denoise_var.h. */
+
 #ifdef __cplusplus
 }
 #endif
