@@ -1387,6 +1387,100 @@ frt_oracle_render_rows_strided(Camera cam, World w, size_t usteps, size_t vsteps
     return 0;
 }
 
+/* pre-order index of target under s, counting as emit does (host/frt_flatten.c): a node, then a group's children in
+ * order or a CSG's left and right operand; *at is the index of s on entry and of the next subtree on return */
+static long
+preorder_find(Shape s, Shape target, long *at)
+{
+    long idx = (*at)++;
+    if (s == target) return idx;
+    if (s->type == SHAPE_GROUP) {
+        for (size_t i = 0; i < s->fields.group.num_children; ++i) {
+            long f = preorder_find(s->fields.group.children + i, target, at);
+            if (f >= 0) return f;
+        }
+    } else if (s->type == SHAPE_CSG) {
+        long f = preorder_find(s->fields.csg.left, target, at);
+        if (f >= 0) return f;
+        return preorder_find(s->fields.csg.right, target, at);
+    }
+    return -1;
+}
+
+static Shape
+preorder_at(Shape s, long want, long *at)
+{
+    if ((*at)++ == want) return s;
+    if (s->type == SHAPE_GROUP) {
+        for (size_t i = 0; i < s->fields.group.num_children; ++i) {
+            Shape f = preorder_at(s->fields.group.children + i, want, at);
+            if (f) return f;
+        }
+    } else if (s->type == SHAPE_CSG) {
+        Shape f = preorder_at(s->fields.csg.left, want, at);
+        if (f) return f;
+        return preorder_at(s->fields.csg.right, want, at);
+    }
+    return NULL;
+}
+
+/* enum shape_enum of the host shape at pre-order index `index` of the world, -1 when there is none */
+int
+frt_oracle_shape_type(World w, long index)
+{
+    long n = 0;
+    for (size_t i = 0; i < w->shapes_num; ++i) {
+        Shape s = preorder_at(w->shapes + i, index, &n);
+        if (s) return (int)s->type;
+    }
+    return -1;
+}
+
+int
+frt_oracle_first_hits(Camera cam, World w, size_t usteps, size_t vsteps, bool jitter, size_t row_begin,
+                      size_t row_end, double *out_t, double *out_normal, int32_t *out_leaf)
+{
+    if (w->global_config == NULL) return -1;
+    for (size_t i = 0; i < w->shapes_num; ++i) warm_bounds(w->shapes + i);
+    octx cx;
+    memset(&cx, 0, sizeof(cx));
+    cx.w = w;
+    size_t at = 0;
+    for (size_t row = row_begin; row < row_end; ++row) {
+        struct sampler smp; /* one table per row, as worker() */
+        sampler_2d(jitter, usteps, vsteps, sampler_default_constraint, &smp);
+        for (size_t px = 0; px < cam->hsize; ++px) {
+            sampler_reset_2d(&smp);
+            for (size_t v = 0; v < vsteps; ++v) {
+                for (size_t u = 0; u < usteps; ++u, ++at) {
+                    size_t idx[2] = {u, v};
+                    double jit[2];
+                    sampler_get_point_2d(&smp, idx, jit);
+                    oray r;
+                    ray_for_pixel(cam, px, row, jit, &r);
+                    intersect_world(&cx, &r, false);
+                    long hi = hit_index(&cx.xs, false);
+                    out_t[at] = -1.0;
+                    out_normal[3 * at] = out_normal[3 * at + 1] = out_normal[3 * at + 2] = 0.0;
+                    out_leaf[at] = -1;
+                    if (hi < 0) continue;
+                    comps cp;
+                    prepare_computations(&cx, hi, &r, &cp);
+                    out_t[at] = cp.t;
+                    memcpy(out_normal + 3 * at, cp.normalv, 3 * sizeof(double));
+                    long n = 0, leaf = -1;
+                    for (size_t i = 0; i < w->shapes_num && leaf < 0; ++i) leaf = preorder_find(w->shapes + i, cp.obj, &n);
+                    out_leaf[at] = (int32_t)leaf;
+                }
+            }
+        }
+        sampler_free(&smp);
+    }
+    free(cx.xs.v);
+    free(cx.container);
+    return 0;
+}
+
 /* rows row_begin, row_begin + 1, ... (out: one row after another) */
 int
 frt_oracle_render_rows(Camera cam, World w, size_t usteps, size_t vsteps, bool jitter,

@@ -45,6 +45,18 @@ int frt_oracle_render_rows_strided(Camera cam, World w, size_t usteps, size_t vs
                                    size_t row_begin, size_t row_end, size_t row_stride, int nthreads, double *out,
                                    frt_oracle_stats *stats);
 
+/*
+ * First hits of the camera samples of rows [row_begin, row_end), in (row, column, sub) order with
+ * sub = v * usteps + u (the features pass's order): per sample the t of hit_index's intersection, comps.normalv as
+ * prepare_computations leaves it (3 doubles) and the leaf's pre-order index, counted as host/frt_flatten.c's emit
+ * counts it; a miss gives t = -1, a zero normal and leaf -1. One thread; the intersector, hit rule and
+ * prepare_computations are the render's own.
+ */
+int frt_oracle_first_hits(Camera cam, World w, size_t usteps, size_t vsteps, bool jitter, size_t row_begin,
+                          size_t row_end, double *out_t, double *out_normal, int32_t *out_leaf);
+/* enum shape_enum of the host shape at that pre-order index of the world, -1 when there is none */
+int frt_oracle_shape_type(World w, long index);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,8 +41,39 @@ def oracle_lib() -> ctypes.CDLL:
         lib.frt_oracle_render_rows_strided.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_bool,
                                                        ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
                                                        vp, ctypes.POINTER(OracleStats)]
+        lib.frt_oracle_first_hits.restype = ctypes.c_int
+        lib.frt_oracle_first_hits.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_bool, ctypes.c_size_t,
+                                              ctypes.c_size_t, vp, vp, vp]
+        lib.frt_oracle_shape_type.restype = ctypes.c_int
+        lib.frt_oracle_shape_type.argtypes = [vp, ctypes.c_long]
         _lib = lib
     return _lib
+
+
+def first_hits(view, row_begin: int = 0, row_end: int | None = None):
+    """The first hit of every camera sample of a captured scene or view, in the features pass's order:
+    (t (rows, width, spp), normal (rows, width, spp, 3), leaf (rows, width, spp) int32) with sub = v * usteps + u;
+    t is hit_index's intersection, normal comps.normalv, leaf the pre-order node index runtime.scene_nodes and
+    GpuRenderer.render_features use. A miss: t = -1, a zero normal, leaf -1."""
+    from fast_ray_tracer_amd.runtime import scene_nodes
+    lib = oracle_lib()
+    row_end = view.height if row_end is None else row_end
+    shape = (row_end - row_begin, view.width, view.usteps * view.vsteps)
+    t = np.zeros(shape, dtype=np.float64)
+    normal = np.zeros(shape + (3,), dtype=np.float64)
+    leaf = np.zeros(shape, dtype=np.int32)
+    host_lib().frt_set_drand48((ctypes.c_ushort * 3)(*view.drand48_state))
+    rc = lib.frt_oracle_first_hits(view.camera, view.world, view.usteps, view.vsteps, view.jitter, row_begin, row_end,
+                                   t.ctypes.data, normal.ctypes.data, leaf.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("oracle first_hits failed (rc=%d)" % rc)
+    hit = leaf >= 0
+    assert np.array_equal(hit, t > 0)
+    types = scene_nodes(view)["type"]
+    assert leaf.max() < len(types)
+    for k in np.unique(leaf[hit]):  # the host shape at that index is the flattened node: same type, a leaf
+        assert lib.frt_oracle_shape_type(view.world, int(k)) == types[k] < 8, (k, types[k])
+    return t, normal, leaf
 
 
 def render(scene, row_begin: int = 0, row_end: int | None = None, threads: int = 0, stats: bool = False,

@@ -59,9 +59,9 @@ def kd_pattern_colours(view):
     return found[0]
 
 
-def sphere_samples(view):
-    """Per camera sample of the view, in (row, col, sub) order with sub = v * usteps + u: t (rows, w, spp; NaN for
-    a miss), the hit point = normal (rows, w, spp, 3), the discriminant (rows, w, spp) and the hit mask."""
+def camera_rays(view):
+    """The camera rays of the view in binary64, in (row, col, sub) order with sub = v * usteps + u: origin and
+    direction, each (rows, w, spp, 3)."""
     cam, tab = flat_camera(view)
     assert cam.aperture_size == 0.0 and cam.jitter == 0
     h, w, spp = int(cam.vsize), int(cam.hsize), tab.shape[0]
@@ -78,7 +78,13 @@ def sphere_samples(view):
     origin = xf_point(0.0, 0.0, 0.0)  # (point aperture: (0.5 - 0.5) * aperture_size)
     v = pixel - origin
     d = v / np.sqrt((v * v).sum(axis=-1, keepdims=True))
-    o = np.broadcast_to(origin, d.shape)
+    return np.broadcast_to(origin, d.shape), d
+
+
+def sphere_samples(view):
+    """Per camera sample of the view, in (row, col, sub) order with sub = v * usteps + u: t (rows, w, spp; NaN for
+    a miss), the hit point = normal (rows, w, spp, 3), the discriminant (rows, w, spp) and the hit mask."""
+    o, d = camera_rays(view)
     a = (d * d).sum(axis=-1)
     b = 2.0 * (o * d).sum(axis=-1)
     c = (o * o).sum(axis=-1) - 1.0

@@ -200,6 +200,8 @@ SCENES = {
     "csg_wide32_48": ("c:csg_wide32_48", {}),
     "csg_wide34_48": ("c:csg_wide34_48", {}),
     "csg_nested_nogroup_96x64": ("c:csg_nested_nogroup_96x64", {}),
+    # every leaf type but CSG, transformed and grouped (make_fixture_primitives.py writes its main.c)
+    "primitives_edge_64x48": ("c:primitives_edge_64x48", {}),
 }
 FIXTURE_YML = os.path.join(HERE, "yml")
 

@@ -36,6 +36,7 @@ EYES = {
     "csg_nested_96x64": ((0.5, 5.0, -10.0), (0.5, 1.0, 0.5)),
     "reflect_refract_160x80": ((-2.6, 1.5, -3.9), (-0.6, 1.0, -0.8)),
     "checkered_torus_120": ((0.0, 5.0, -10.0), (0.0, 0.0, 0.0)),
+    "primitives_edge_64x48": ((1.02, 7.1, -13.0), (0.2, 0.8, 0.3)),
 }
 
 
@@ -142,7 +143,7 @@ def test_features_are_a_placement(built, name, size):
 
 PATH_SCENES = {"cornell_direct_64_4x4": (64, 64), "csg_ops_96x64": (48, 32), "bump_map_100": (48, 48),
                "checkered_sphere_dof_100": (32, 32), "checkered_sphere_jitter_100": (32, 32),
-               "teapot_low_100": (40, 40)}
+               "teapot_low_100": (40, 40), "primitives_edge_64x48": (64, 48)}
 PATH_ENVS = {"default": {}, "jit_trace_off": {"FRT_JIT_TRACE": "0"}, "uniform_off": {"FRT_PREPARE_UNIFORM": "0"},
              "mesh_off": {"FRT_MESH": "0"}}
 

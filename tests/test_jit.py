@@ -209,7 +209,7 @@ def test_tile_and_sub_part_kernels_equal_generic_walk(built, name, tmp_path):
 @pytest.mark.parametrize("name", ["cornell_direct_64_4x4", "checkered_torus_120", "checkered_cylinder_120", "group_test_150x50",
                                   "teapot_low_100", "checkered_sphere_dof_100", "patterns_160x80", "cornell_gi_16",
                                   "test_scene_120", "bump_map_100"] + CSG_ELIGIBLE + sorted(CSG_REFUSED)
-                         + ["csg_nested_nogroup_96x64"])
+                         + ["csg_nested_nogroup_96x64", "primitives_edge_64x48"])
 def test_jit_closest_hit_equals_generic_walk(built, name, tmp_path):
     """The scene-specialised closest-hit kernel (frt_jit_trace: binary32 intervals, the winner's t from its own leaf
     in binary64, the rays it cannot settle handed to the generic walk by k_trace_redo) against k_trace for every
