@@ -186,3 +186,19 @@ frt_accum_device_part(frt_accum *acc)
 {
     return acc != NULL ? acc->dev : NULL;
 }
+
+int
+frt_accum_host_state(frt_accum *acc, int64_t *npixels, int32_t **n, double **mean, double **m2, uint64_t **frames,
+                     uint64_t **skipped)
+{
+    if (acc == NULL || acc->dev != NULL) {
+        return -1;
+    }
+    *npixels = acc->npixels;
+    *n = acc->n;
+    *mean = acc->mean;
+    *m2 = acc->m2;
+    *frames = &acc->frames;
+    *skipped = &acc->skipped;
+    return 0;
+}

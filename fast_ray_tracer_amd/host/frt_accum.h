@@ -24,6 +24,10 @@ int frt_accum_resolve(frt_accum *acc, double *mean_rgba, double *var, int on_dev
 void frt_accum_release(frt_accum *acc);
 /* the device accumulator inside (frt_render_rows_accumulate takes it), NULL for a host accumulator */
 frt_accum_dev *frt_accum_device_part(frt_accum *acc);
+/* a host accumulator's state in place (n, 4 x mean, 3 x m2 per pixel) and its two counters, for the passes of
+ * libfrt_host that write one (host/frt_reproject.c); -1 for NULL or a device accumulator */
+int frt_accum_host_state(frt_accum *acc, int64_t *npixels, int32_t **n, double **mean, double **m2, uint64_t **frames,
+                         uint64_t **skipped);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,7 @@ libfrt_device.so or a GPU is missing, construction raises.
 from __future__ import annotations
 
 import ctypes
+import numbers
 import os
 import weakref
 import threading
@@ -194,6 +195,50 @@ class AccumStats(ctypes.Structure):
                 "device": int(self.device), "add_ms": float(self.add_ms), "resolve_ms": float(self.resolve_ms)}
 
 
+class FlatCamera(ctypes.Structure):
+    """frt_camera (include/frt_device.h): a camera as the engine takes it (flat_camera(view))."""
+    _fields_ = [("hsize", ctypes.c_int64), ("vsize", ctypes.c_int64), ("usteps", ctypes.c_int64),
+                ("vsteps", ctypes.c_int64), ("half_width", ctypes.c_double), ("half_height", ctypes.c_double),
+                ("pixel_size", ctypes.c_double), ("canvas_distance", ctypes.c_double), ("inv", ctypes.c_double * 16),
+                ("aperture_size", ctypes.c_double), ("aperture_type", ctypes.c_int32), ("jitter", ctypes.c_int32),
+                ("aperture_args", ctypes.c_double * 4)]
+
+
+class ReprojectParams(ctypes.Structure):
+    """frt_reproject_params (include/frt_device.h "Reprojection"). ReprojectParams() holds the library's defaults
+    (frt_reproject_defaults); keyword arguments replace single fields: ReprojectParams(max_history=8)."""
+    _fields_ = [("max_history", ctypes.c_int32), ("match_material", ctypes.c_int32), ("normal_cos", ctypes.c_double),
+                ("sigma_depth", ctypes.c_double), ("min_weight", ctypes.c_double)]
+
+    def __init__(self, **fields):
+        super().__init__()
+        host_lib().frt_reproject_defaults(ctypes.byref(self))
+        for k, v in fields.items():
+            if k not in dict(self._fields_):
+                raise TypeError("frt: ReprojectParams has no field %r" % (k,))
+            setattr(self, k, v)
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class ReprojectStats(ctypes.Structure):
+    """frt_reproject_stats (include/frt_device.h "Reprojection")."""
+    _fields_ = [("pixels", ctypes.c_uint64), ("reprojected", ctypes.c_uint64), ("missed", ctypes.c_uint64),
+                ("no_history", ctypes.c_uint64), ("device", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("kernel_ms", ctypes.c_double), ("host_ms", ctypes.c_double)]
+
+    def as_dict(self) -> dict:
+        return {"pixels": int(self.pixels), "reprojected": int(self.reprojected), "missed": int(self.missed),
+                "no_history": int(self.no_history), "device": int(self.device), "kernel_ms": float(self.kernel_ms),
+                "host_ms": float(self.host_ms)}
+
+
+class ReprojectGeometry(ctypes.Structure):
+    """frt_reproject_geometry: what frt_reproject_setup derives from the two cameras (reproject_setup())."""
+    _fields_ = [("o_cur", ctypes.c_double * 3), ("o_prev", ctypes.c_double * 3), ("prev_fwd", ctypes.c_double * 16)]
+
+
 def host_lib(auto_build: bool = False) -> ctypes.CDLL:
     """Load libfrt_host.so (which pulls in libfrt_device.so) with global symbols."""
     global _host
@@ -332,6 +377,26 @@ def host_lib(auto_build: bool = False) -> ctypes.CDLL:
         lib.frt_accum_error.restype = ctypes.c_char_p
         lib.frt_render_rows_accumulate.restype = ctypes.c_int
         lib.frt_render_rows_accumulate.argtypes = [vp, fp, ctypes.c_int32, vp, fs]
+        lib.frt_camera_size.restype = ctypes.c_size_t
+        if lib.frt_camera_size() != ctypes.sizeof(FlatCamera):
+            raise RuntimeError("frt: frt_camera is %d bytes in %s, runtime.py FlatCamera %d: rebuild"
+                               % (lib.frt_camera_size(), build.HOST_LIB, ctypes.sizeof(FlatCamera)))
+        for fn, mirror in (("frt_reproject_params_size", ReprojectParams), ("frt_reproject_stats_size", ReprojectStats)):
+            getattr(lib, fn).restype = ctypes.c_size_t
+            if getattr(lib, fn)() != ctypes.sizeof(mirror):
+                raise RuntimeError("frt: %s() is %d bytes in %s, runtime.py %s %d: rebuild"
+                                   % (fn, getattr(lib, fn)(), build.HOST_LIB, mirror.__name__, ctypes.sizeof(mirror)))
+        rpp, rps, fcp = ctypes.POINTER(ReprojectParams), ctypes.POINTER(ReprojectStats), ctypes.POINTER(FlatCamera)
+        lib.frt_reproject_defaults.restype = None
+        lib.frt_reproject_defaults.argtypes = [rpp]
+        lib.frt_reproject_setup.restype = ctypes.c_int
+        lib.frt_reproject_setup.argtypes = [fcp, fcp, ctypes.POINTER(ReprojectGeometry)]
+        lib.frt_accum_reproject.restype = ctypes.c_int
+        lib.frt_accum_reproject.argtypes = [vp, vp, fcp, fcp, fb, fb, i64, i64, rpp, ctypes.c_int, rps]
+        lib.frt_accum_reproject_cameras.restype = ctypes.c_int
+        lib.frt_accum_reproject_cameras.argtypes = [vp, vp, vp, vp, fb, fb, i64, i64, rpp, ctypes.c_int, rps]
+        lib.frt_accum_host_state.restype = ctypes.c_int
+        lib.frt_accum_host_state.argtypes = [vp, ctypes.POINTER(i64)] + [ctypes.POINTER(vp)] * 5
         _host = lib
         return lib
 
@@ -774,6 +839,12 @@ class GpuRenderer:
                           "device", self.device, mean.data_ptr(), var.data_ptr())
         return mean.cpu().numpy(), var.cpu().numpy(), st.as_dict()
 
+    def temporal(self, params=None, seed: int = 0x5EED) -> "TemporalAccumulator":
+        """A TemporalAccumulator over this renderer: accumulation that follows a moving camera. Each of its render()
+        calls moves the camera, reprojects the accumulated history into the new view on the device
+        (frt_accum_reproject) and adds the call's frames. params: a ReprojectParams, a dict of its fields, or None."""
+        return TemporalAccumulator(self, params, seed)
+
 
 def render_multi(scene: Scene, devices: str | None = None) -> np.ndarray:
     """The drop-in entry point itself: ``render_multi(cam, world, usteps, vsteps, jitter)``
@@ -1214,10 +1285,210 @@ class Accumulator:
     def reset(self) -> None:
         self._check(self.lib.frt_accum_reset(self._acc))
 
+    def state(self):
+        """A host accumulator's state as copies: (n (npixels,) int32, mean (npixels, 4), m2 (npixels, 3)). A device
+        accumulator's state stays on the device: resolve() is its way out."""
+        vp = ctypes.c_void_p
+        npx, ptr = ctypes.c_int64(), [vp() for _ in range(5)]
+        if self.lib.frt_accum_host_state(self._acc, ctypes.byref(npx), *[ctypes.byref(q) for q in ptr]) != 0:
+            raise RuntimeError("frt: accumulator: state() needs a host accumulator (device=None)")
+        n = np.ctypeslib.as_array(ctypes.cast(ptr[0], ctypes.POINTER(ctypes.c_int32)), (npx.value,)).copy()
+        mean = np.ctypeslib.as_array(ctypes.cast(ptr[1], ctypes.POINTER(ctypes.c_double)), (npx.value, 4)).copy()
+        m2 = np.ctypeslib.as_array(ctypes.cast(ptr[2], ctypes.POINTER(ctypes.c_double)), (npx.value, 3)).copy()
+        return n, mean, m2
+
     def close(self) -> None:
         if getattr(self, "_acc", None):
             self.lib.frt_accum_release(self._acc)
             self._acc = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def flat_camera(view) -> FlatCamera:
+    """A Scene's or View's camera as the engine's frt_camera (frt_flatten_camera, without a sample table); a
+    FlatCamera comes back as it is."""
+    if isinstance(view, FlatCamera):
+        return view
+    lib = host_lib()
+    lib.frt_flatten_camera.restype = ctypes.c_int
+    lib.frt_flatten_camera.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_bool,
+                                       ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
+    cam, table = FlatCamera(), ctypes.c_void_p()
+    if lib.frt_flatten_camera(view.camera, 0, 0, False, ctypes.addressof(cam), ctypes.byref(table)) != 0:
+        raise RuntimeError("frt: frt_flatten_camera failed")
+    return cam
+
+
+def reproject_setup(prev_view, cur_view) -> ReprojectGeometry:
+    """frt_reproject_setup: the two lens centres and the previous camera's forward matrix, as both passes take them.
+    It raises for cameras whose sizes differ or whose matrices are not finite."""
+    lib = host_lib()
+    g = ReprojectGeometry()
+    if lib.frt_reproject_setup(ctypes.byref(flat_camera(prev_view)), ctypes.byref(flat_camera(cur_view)),
+                               ctypes.byref(g)) != 0:
+        raise RuntimeError("frt: reproject: " + lib.frt_accum_error().decode())
+    return g
+
+
+def _reproject_params(params) -> ReprojectParams:
+    if params is None:
+        return ReprojectParams()
+    if isinstance(params, ReprojectParams):
+        return params
+    if isinstance(params, dict):
+        return ReprojectParams(**params)
+    raise TypeError("frt: reproject params must be a ReprojectParams, a dict of its fields or None")
+
+
+def _reproject_features(features, npixels: int, keep: list):
+    """(FeatureBuffers, on_device) of render_features' dict, a (geom, ids) pair of arrays, or a (geom, ids) pair of
+    device pointers."""
+    if not isinstance(features, dict) and all(isinstance(x, numbers.Integral) for x in features):
+        return FeatureBuffers(int(features[0]) or None, int(features[1]) or None), True
+    geom, ids = _feature_buffers(features)
+    if geom.size != npixels * FEATURE_GEOM_WORDS or ids.size != npixels * 2:
+        raise ValueError("frt: reproject needs feature buffers of the cameras' %d pixels: geom %r, ids %r"
+                         % (npixels, geom.shape, ids.shape))
+    keep += [geom, ids]
+    return FeatureBuffers(geom.ctypes.data, ids.ctypes.data), False
+
+
+def reproject(dst: "Accumulator", src: "Accumulator", prev_view, prev_features, cur_view, cur_features, params=None,
+              stats: bool = False):
+    """Carry src's state, accumulated under prev_view, to cur_view's pixels in dst (frt_accum_reproject: SVGF's
+    reprojection step; include/frt_device.h "Reprojection"). dst and src are two Accumulators of the views' size,
+    both on the host (the C pass, which is the definition) or both on one device (k_accum_reproject); the two give
+    the same bits. prev_view / cur_view: a Scene, a View or a FlatCamera; the features are the dicts render_features
+    returns under each view (or (geom, ids) arrays), or for device accumulators (geom_ptr, ids_ptr) pairs of device
+    memory. dst's earlier contents are gone afterwards; later add()s continue from the reprojected state. A pixel
+    whose surface the previous view did not see starts over with n = 0. params: a ReprojectParams, a dict of its
+    fields, or None. Returns None (with stats=True: the ReprojectStats)."""
+    lib = host_lib()
+    prev, cur = flat_camera(prev_view), flat_camera(cur_view)
+    w, h = int(cur.hsize), int(cur.vsize)
+    keep = []
+    pf, pdev = _reproject_features(prev_features, w * h, keep)
+    cf, cdev = _reproject_features(cur_features, w * h, keep)
+    if pdev != cdev:
+        raise ValueError("frt: reproject needs both views' features on the host or both on the device")
+    p = _reproject_params(params)
+    st = ReprojectStats()
+    rc = lib.frt_accum_reproject(dst._acc, src._acc, ctypes.byref(prev), ctypes.byref(cur), ctypes.byref(pf),
+                                 ctypes.byref(cf), w, h, ctypes.byref(p), int(pdev), ctypes.byref(st))
+    if rc != 0:
+        raise RuntimeError("frt: reproject: " + lib.frt_accum_error().decode())
+    return st if stats else None
+
+
+class TemporalAccumulator:
+    """Accumulation over a sequence of views of one resident scene (GpuRenderer.temporal()): every render() call
+    reprojects the history into the call's view and adds the call's frames to it, all on the device.
+
+    The contract: the result of a sequence of render() calls is bit for bit the same composition done by hand with a
+    host Accumulator pair: for call j with view v_j, frames f_j and first frame index k_j (the frames of the object's
+    life so far), feats_j = render_features(seed=seed + k_j, batch_samples=...) under v_j; reproject(dst, src,
+    v_{j-1}, feats_{j-1}, v_j, feats_j, params) (skipped on the first call and after a restart); dst.add(render(
+    seed=seed + k_j + i, ...)) for i < f_j; dst.resolve(). Frame k of the object's life uses seed + k, wrapping at 64
+    bits. A view whose size differs from the history's restarts the history (counted in `restarts`)."""
+
+    def __init__(self, renderer: "GpuRenderer", params=None, seed: int = 0x5EED):
+        self.r = renderer
+        self.params = _reproject_params(params)
+        self.seed = int(seed)
+        self.frames_done = 0
+        self.restarts = 0
+        self._accs = [None, None]
+        self._feats = [None, None]
+        self._cur = 0
+        self._prev_cam = None
+        self._shape = None
+
+    def reset(self) -> None:
+        """Forget the history (the seeds run on)."""
+        self._prev_cam = None
+        for a in self._accs:
+            if a is not None:
+                a.reset()
+
+    def close(self) -> None:
+        for a in self._accs:
+            if a is not None:
+                a.close()
+        self._accs = [None, None]
+        self._feats = [None, None]
+        self._prev_cam = None
+        self._shape = None
+
+    def _allocate(self, h: int, w: int) -> None:
+        import torch
+        self.close()
+        self._accs = [Accumulator((h, w), device=self.r.device) for _ in range(2)]
+        with torch.cuda.device(self.r.device):
+            self._feats = [(torch.empty((h, w, FEATURE_GEOM_WORDS), dtype=torch.float64, device="cuda"),
+                            torch.empty((h, w, 2), dtype=torch.int32, device="cuda")) for _ in range(2)]
+        self._shape = (h, w)
+
+    def render(self, view=None, frames: int = 1, batch_samples: int = 0, precision: str | None = None, denoise=None,
+               stats: bool = False):
+        """Move the camera to `view` (None: where it is), reproject the history into it, add `frames` frames and
+        resolve: (mean (h, w, 4), var (h, w, 4)) as render_accumulated returns them, var[..., 3] the samples a pixel
+        holds (the reprojected history's and the new frames'). denoise: None, or True / a DenoiseVarParams / a dict
+        of its fields to run the variance-guided denoise on the device buffers before they come back; it needs
+        frames >= 2 and raises otherwise, as render_accumulated_denoised does. With stats=True a third value: a dict
+        with "reproject" (ReprojectStats.as_dict(), None when nothing was reprojected), "frame" (the summed
+        FrameStats), "restarts", "first_frame" and, with denoise, "denoise"."""
+        import torch
+        if frames < 1:
+            raise ValueError("frt: temporal render needs frames >= 1, not %r" % (frames,))
+        if denoise is not None and denoise is not False and frames < 2:
+            raise ValueError("frt: temporal render with denoise needs frames >= 2 (one frame has no variance), not %r"
+                             % (frames,))
+        r = self.r
+        if view is not None:
+            r.set_camera(view)
+        h, w = r.frame.height, r.frame.width
+        cam = flat_camera(r.frame)
+        if self._shape is not None and self._shape != (h, w):
+            self.restarts += 1
+            self._prev_cam = None
+        if self._shape != (h, w):
+            self._allocate(h, w)
+        seed0 = (self.seed + self.frames_done) & 0xFFFFFFFFFFFFFFFF
+        src, dst = self._cur, self._cur ^ 1
+        geom, ids = self._feats[dst]
+        r.render_features_into(geom.data_ptr(), ids.data_ptr(), seed=seed0, batch_samples=batch_samples)
+        rst = None
+        if self._prev_cam is not None:
+            pgeom, pids = self._feats[src]
+            rst = reproject(self._accs[dst], self._accs[src], self._prev_cam, (pgeom.data_ptr(), pids.data_ptr()),
+                            cam, (geom.data_ptr(), ids.data_ptr()), self.params, stats=True)
+        else:
+            self._accs[dst].reset()
+        fst = r._accumulate(self._accs[dst], frames, seed0, batch_samples, precision, stats)
+        self.frames_done += frames
+        self._cur, self._prev_cam = dst, cam
+        with torch.cuda.device(r.device):
+            mean = torch.empty((h, w, 4), dtype=torch.float64, device="cuda")
+            var = torch.empty((h, w, 4), dtype=torch.float64, device="cuda")
+        self._accs[dst].resolve_into(mean.data_ptr(), var.data_ptr())
+        dst_stats = None
+        if denoise is not None and denoise is not False:
+            dst_stats = _denoise_var(mean.data_ptr(), var.data_ptr(), geom.data_ptr(), ids.data_ptr(), True, w, h, 1,
+                                     None if denoise is True else denoise, "device", r.device, mean.data_ptr(),
+                                     var.data_ptr())
+        out = (mean.cpu().numpy(), var.cpu().numpy())
+        if not stats:
+            return out
+        info = {"reproject": rst.as_dict() if rst is not None else None, "frame": fst, "restarts": self.restarts,
+                "first_frame": self.frames_done - frames}
+        if dst_stats is not None:
+            info["denoise"] = dst_stats.as_dict()
+        return out + (info,)
 
     def __del__(self):
         try:

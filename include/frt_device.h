@@ -745,6 +745,101 @@ void frt_denoise_var_release(void);
 
 /* frt_denoise_var_host and frt_denoise_var (backend choice) are libfrt_host's: host/frt_denoise_var.h. */
 
+/*
+ * Reprojection (fast_ray_tracer_amd/csrc/frt_accum.hip k_accum_reproject, host/frt_reproject.c; DESIGN.md "Temporal
+ * reprojection"): SVGF's reprojection step (Schied et al. 2017). It carries an accumulator's state from the pixels of
+ * the camera it was accumulated under (prev) to the pixels of a moved camera (cur), and drops it where the surface a
+ * current pixel sees was not visible before. The host pass (frt_reproject_host, libfrt_host) is the definition; the
+ * device pass repeats it operation for operation in binary64 (+ - * /, sqrt, floor, comparisons and exact integer
+ * conversions only, no fused multiply-add), so the two agree bit for bit.
+ *
+ * Inputs: a source accumulator src (accumulated under prev) and a destination accumulator dst != src of the same
+ * npixels = w x h; the feature buffers of both views as frt_feature_buffers lays them out (prev_geom, prev_ids,
+ * cur_geom, cur_ids; of geom only depth [0] and normal [1..3] are read); the two frt_cameras, whose hsize x vsize are
+ * both w x h; frt_reproject_params.
+ * xf_point(m, p)[r] = ((m[4r]*p[0] + m[4r+1]*p[1]) + m[4r+2]*p[2]) + m[4r+3] for r = 0..2; a.b and |a|^2 of
+ * 3-vectors are (a0*b0 + a1*b1) + a2*b2.
+ *
+ * Setup (frt_reproject_setup, host only, once per call; both passes take its doubles): O_cur = xf_point(cur.inv,
+ * (0,0,0)), O_prev likewise (the lens centre when there is an aperture), and prev_fwd, the inverse of prev.inv by the
+ * host library's matrix_inverse. It refuses cameras whose sizes differ or are not positive, and a camera matrix,
+ * scalar (half_width, half_height, pixel_size, canvas_distance) or inverse that is not finite.
+ *
+ * Per destination pixel p = (px, py), index py * w + px, with outcome 0 reprojected, 1 current pixel without a hit,
+ * 2 no history:
+ * 1. Valid: cur_ids.node >= 0 and the current depth d finite and > 0. Otherwise the all-zero state, outcome 1.
+ * 2. World point: ray_for_pixel's centre ray with the point aperture: xoff = ((double)px + 0.5) * cur.pixel_size,
+ *    yoff likewise with py; P = xf_point(cur.inv, (cur.half_width - xoff, cur.half_height - yoff,
+ *    -cur.canvas_distance)); v = P - O_cur; dir = v * (1.0 / sqrt(|v|^2)); W[k] = O_cur[k] + d * dir[k].
+ * 3. Into the previous camera: c = xf_point(prev_fwd, W); outcome 2 unless c.z is finite and < 0.
+ *    s = -prev.canvas_distance / c.z; fx = (prev.half_width - c.x * s) / prev.pixel_size - 0.5; fy likewise with
+ *    half_height and c.y. A coordinate within 2^-20 of a whole pixel is that pixel: rx = floor(fx + 0.5), and
+ *    fx = rx where |fx - rx| <= 2^-20; fy likewise. (Under an unmoved camera fx misses px by the rounding of this
+ *    chain alone; snapped, the pixel's own tap weighs exactly 1 and the others exactly 0, and the state comes through
+ *    unchanged instead of blurred by 2^-50 of its neighbours. A camera move that shifts a surface by less than
+ *    2^-20 of a pixel, about 1e-6, is therefore no move for that surface.) Outcome 2 unless fx >= -1.0 &&
+ *    fx < (double)w && fy >= -1.0 && fy < (double)h (a NaN fails): the test comes before any conversion to an integer.
+ *    x0 = (int)floor(fx), tx = fx - (double)x0; y0, ty likewise.
+ * 4. Expected previous depth: e = sqrt(|W - O_prev|^2). (Beyond about 1e154 the square overflows and an infinite e
+ *    accepts every previous depth; first-hit depths are nowhere near.)
+ * 5. Taps q in the order (x0,y0), (x0+1,y0), (x0,y0+1), (x0+1,y0+1) with weights (1-tx)*(1-ty), tx*(1-ty),
+ *    (1-tx)*ty, tx*ty. A tap is accepted when it lies inside the image; src.n_q > 0; prev_ids.node_q == cur_ids.node_p
+ *    (and the material ids are equal when match_material); the previous depth z_q is finite and > 0 and
+ *    |z_q - e| <= sigma_depth * e; and with dn = n_p . n_q, nn_p = |n_p|^2, nn_q = |n_q|^2: dn > 0 and
+ *    dn*dn >= (normal_cos*normal_cos) * (nn_p*nn_q). The state of a tap is read only when it is accepted.
+ * 6. Sums over the accepted taps in that order, from 0.0: ws += w; am[ch] += w * mean_q[ch] (4 channels);
+ *    av[ch] += w * (m2_q[ch] / (double)n_q) (3 channels); an += w * (double)n_q. Outcome 2 when ws < min_weight.
+ * 7. New state: mean[ch] = am[ch] / ws; r = an / ws + 0.5; n = max_history where r >= (double)max_history, else
+ *    (int32)r (truncated: an / ws rounded to the nearest count, since the quotient of taps that all hold n samples may
+ *    round to just under n), and at least 1; m2[ch] = (av[ch] / ws) * (double)n. Outcome 2 leaves the all-zero state.
+ *
+ * dst's previous contents are overwritten (a reset, then the fill): its frames become min(src.frames, max_history),
+ * its skipped 0, and later adds continue Welford's update from this state unchanged, so a history capped at
+ * max_history behaves like an exponential average whose newest frame weighs at least 1 / (max_history + 1).
+ */
+typedef struct frt_reproject_params {
+    int32_t max_history;    /* 1..2^20 (default 32): the count a reprojected pixel keeps at most */
+    int32_t match_material; /* 0 or 1 (default 1): taps of another material id are rejected */
+    double normal_cos;      /* (0, 1] (default 0.9): smallest cosine between the two normals */
+    double sigma_depth;     /* > 0 (default 0.02): relative depth difference a tap may have */
+    double min_weight;      /* (0, 1] (default 2^-6): smallest sum of accepted bilinear weights */
+} frt_reproject_params;
+
+typedef struct frt_reproject_stats {
+    uint64_t pixels;
+    uint64_t reprojected; /* outcome 0 */
+    uint64_t missed;      /* outcome 1 */
+    uint64_t no_history;  /* outcome 2 */
+    int32_t device;       /* the HIP device, -1 for host accumulators */
+    int32_t reserved;     /* 0 */
+    double kernel_ms;     /* k_accum_reproject (HIP events; 0 on the host) */
+    double host_ms;       /* the host pass (0 on the device) */
+} frt_reproject_stats;
+
+/* what frt_reproject_setup derives from the two cameras */
+typedef struct frt_reproject_geometry {
+    double o_cur[3], o_prev[3];
+    double prev_fwd[16];
+} frt_reproject_geometry;
+
+/*
+ * The device pass. src and dst are on one device; the four feature buffers are all in host memory (on_device 0: they
+ * are uploaded into scratch the destination keeps) or all in device memory on that device. geometry is
+ * frt_reproject_setup's (libfrt_host, host/frt_reproject.h). stats may be NULL. Refusals (-1, the reason in
+ * frt_accum_error, every output untouched): a null pointer; dst == src; cameras whose sizes differ from w x h, or
+ * w * h != npixels of either accumulator; more than 262140 rows (a block is 4 rows, the launch grid 65535 blocks
+ * high); accumulators on different devices; a parameter out of range or not finite (the ranges are checked here as
+ * in libfrt_host's frt_reproject_params_reason, for callers that come without frt_accum_reproject).
+ */
+int frt_accum_dev_reproject(frt_accum_dev *dst, const frt_accum_dev *src, const frt_camera *prev_cam,
+                            const frt_camera *cur_cam, const frt_reproject_geometry *geometry,
+                            const frt_feature_buffers *prev_features, const frt_feature_buffers *cur_features,
+                            int64_t w, int64_t h, const frt_reproject_params *params, int on_device,
+                            frt_reproject_stats *stats);
+
+/* frt_reproject_defaults, frt_reproject_params_size, frt_reproject_stats_size, frt_reproject_setup,
+ * frt_reproject_host and frt_accum_reproject are libfrt_host's: host/frt_reproject.h. */
+
 #ifdef __cplusplus
 }
 #endif
